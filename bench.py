@@ -14,8 +14,13 @@ the ranks; started plainly, `bench.py --gpus N` spawns its own N ranks (torch.di
 this process has touched a GPU - the reference starts its ranks itself too, joeynmt/__main__.py:72-79) and exits with the
 child's code.  Rank 0 prints the JSON line either way.
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel = bf16 MFMA GEMM, HIP-event timed on its
-launch stream) and `cpu_baseline` (the CPU oracle restatement on a bounded sample) objects.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); `--full` adds the side figures behind it: graph-launch host time, the other gradient exchange, the `roofline`
+(dominant kernel = bf16 MFMA GEMM, HIP-event timed on its launch stream), the config-faithful and per-config steps, the fp32
+mode, the beam-5 decode and `cpu_baseline` (the CPU oracle restatement on a bounded sample).
+
+`--dump-outputs DIR` writes what the timed step handed its caller after the last timed step, as float32 .npy files (see
+dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -191,7 +196,9 @@ def build_step(device, world, dtype=torch.bfloat16, seed=42, ragged=False, host_
         # single GPU: the whole step incl. the update is ONE captured graph.  Data parallel: the same kernels in the same
         # order, cut where the RCCL calls go: forward + backward (the deferred weight-gradient products stay queued:
         # flush=False), then one piece per weight-gradient group, then the update (see capture()).
-        return step.micro_step(state["batch"], sort=False, update=not ddp, overlap=False, flush=not ddp, cut_hook=cut_hook)
+        # state["loss"]: the step's normalised loss - under capture the graph's own output, which every replay rewrites
+        state["loss"] = step.micro_step(state["batch"], sort=False, update=not ddp, overlap=False, flush=not ddp, cut_hook=cut_hook)
+        return state["loss"]
 
     def grad_only():
         """forward + backward + the deferred weight-gradient products of the bench batch, no update: the flat gradient stays"""
@@ -1138,11 +1145,42 @@ def decode_extras(device, beam=5, alpha=1.0, max_len=100):
     return out
 
 
+DUMP_PARAM_SAMPLE = 1 << 22  # parameter entries written by --dump-outputs: 16 MB of float32
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, model, step, state):
+    """--dump-outputs DIR: what the timed step handed its caller after the last timed step, as float32 .npy files.
+      loss.npy            [1]  the step's normalised loss (TrainStep.micro_step's return value)
+      grad_norm_clip.npy  [2]  the gradient norm of the update and the clip coefficient applied to it
+      params_sample.npy   [DUMP_PARAM_SAMPLE]  the updated parameters, concatenated in model.named_parameters() order,
+                          at fixed seeded positions (sorted); the whole set is ~90 M entries
+    The inputs are seeded; the step's floating-point atomic sums make two runs agree to rounding, not bit for bit
+    (JS2T_DETERMINISTIC=1 selects the ordered sums)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (min(DUMP_PARAM_SAMPLE, flat.numel()), ), generator=g).sort().values
+        arrays = {"loss": state["loss"].detach().float().reshape(1), "grad_norm_clip": step.optimizer.norm_clip.detach().float(),
+                  "params_sample": flat[idx.to(flat.device)]}
+        for name, t in arrays.items():
+            np.save(out_dir / f"{name}.npy", t.cpu().numpy().astype(np.float32))
+        del flat
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --varying: 100)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 5; --varying: 60)")
+    ap.add_argument("--full", action="store_true",
+                    help="the side figures too (graph-launch host time, other exchange, roofline, config-faithful and per-config steps, "
+                         "fp32 mode, decode, CPU baseline); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (loss, gradient norm, parameter sample) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying a hipGraph")
@@ -1153,6 +1191,15 @@ def main():
     ap.add_argument("--host-inputs", action="store_true", help="copy the waveforms from pinned host memory every step (PCIe-inclusive rate; not the headline value)")
     ap.add_argument("--varying", action="store_true", help="side figure only: a new ragged batch every step (TokenBatchSampler + PrefetchLoader + one hipGraph per shape bucket)")
     args = ap.parse_args()
+    if args.varying and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline step's outputs: not with --varying")
+    if args.steps is None:
+        args.steps = 100 if args.varying else 20
+    if args.warmup is None:
+        args.warmup = 60 if args.varying else 5
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the result line - every side leg stays off
+        args.no_cpu_baseline = args.no_roofline = args.no_decode = args.no_extras = True
 
     # JS2T_BENCH_BACKEND=gloo + several ranks on one card rehearses the N > 1 code path on a single-GPU box
     # (gradient exchange through gloo instead of RCCL); never set by the driver
@@ -1185,7 +1232,7 @@ def main():
     if args.varying:
         if world != 1:
             sys.exit("bench.py --varying: single GPU")
-        res = varying_bench(device, args.steps if args.steps != 20 else 100, args.warmup if args.warmup != 5 else 60, use_graphs=not args.no_graph)
+        res = varying_bench(device, args.steps, args.warmup, use_graphs=not args.no_graph)
         print(json.dumps({"metric": "audio frames/sec (train step, varying batches)", "value": res["frames_per_s_unpadded"], "unit": "frames/s",
                           "n_gpus": 1, "ms_per_step": res["ms_per_step"], "higher_is_better": True, "dtype": "bf16", "data": "synthetic",
                           "config": {"workload": "configs/librispeech_100h.yaml ASR train step, a new batch every step"}, "varying": res}), flush=True)
@@ -1228,11 +1275,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, step, state)
     stats = step.read_stats()
     # how much of a step the HOST spends inside the launch of its graph(s): with the GPU idle (synchronised before each launch) the
     # call returns when the ~900 nodes are enqueued.  A step cannot be shorter than this on this runtime.
     launch_host_ms = None
-    if use_graph:
+    if use_graph and args.full:
         # N > 1: a step is collectives too - EVERY rank runs these eight steps (never a subset of the ranks); the figure is rank 0's:
         # what its host spends launching the step's ~15 graphs and handing the ranges to RCCL between them, with the GPU idle
         ts = []
@@ -1252,7 +1301,7 @@ def main():
         exchange_times = {headline_dtype: round(elapsed / args.steps * 1e3, 3)}
         # the other exchange as a side figure: collectives are never captured, so the reducer's staging dtype is a host-side switch
         # between two replays - every rank flips it at the same point.  (RCCL only: gloo has no bf16 staging path.)
-        if torch.distributed.get_backend() == "nccl" and os.environ.get("JS2T_BENCH_ONE_EXCHANGE", "0") != "1":
+        if args.full and torch.distributed.get_backend() == "nccl" and os.environ.get("JS2T_BENCH_ONE_EXCHANGE", "0") != "1":
             try:
                 other = None if headline_dtype == "bf16" else torch.bfloat16
                 keep = step.reducer.comm_dtype

@@ -180,7 +180,7 @@ def test_bench_two_ranks_end_to_end(device, ranks):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(ranks), "--steps", "3" if ranks == 2 else "2", "--warmup", "2" if ranks == 2 else "1",
-                          "--no-cpu-baseline", "--no-decode", "--no-roofline"], cwd=str(root), env=env, capture_output=True, text=True, timeout=1500)
+                          "--full", "--no-cpu-baseline", "--no-decode", "--no-roofline"], cwd=str(root), env=env, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]

@@ -1,6 +1,7 @@
 set -e -o pipefail
 export TMPDIR=/tmp
-mkdir -p gpurun_out/prof12
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-decode --no-roofline > gpurun_out/prof12/bench.json 2> gpurun_out/prof12/err.log
-cp /tmp/prof_kt/*kernel_stats.csv gpurun_out/prof12/kernel_stats.csv
-python tools/kstats.py gpurun_out/prof12 27 40
+out=${1:?usage: bash tools/prof_train.sh OUT_DIR}
+mkdir -p $out
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-decode --no-roofline > $out/bench.json 2> $out/err.log
+cp /tmp/prof_kt/*kernel_stats.csv $out/kernel_stats.csv
+python tools/kstats.py $out 27 40
