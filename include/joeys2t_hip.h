@@ -426,6 +426,25 @@ int js2t_ctc_bwd(const void* logits, int dt, const float* lse, const int64_t* ta
                  float scale, void* dlogits, int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t blank,
                  int zero_infinity, int beta_ready, const int32_t* row_offsets, int64_t packed_rows, js2t_stream stream);
 
+/* EXTENSION (the reference has no aligner): CTC forced alignment - the best path of the recursion above, max in place of
+ * logaddexp, with back-pointers and the back-trace in the same launch.  logits / lse / targets / in_len / tgt_len / blank /
+ * row_offsets, the length clamps and the limit on 2*Lmax+1 as in js2t_ctc_alpha.  f32 throughout, one rounding per step:
+ *   v_0(s) = lp_0(s) for s < 2, else -inf;  v_t(s) = lp_t(s) + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) where the skip is allowed)
+ * Ties (part of the contract): a predecessor replaces the best so far only if strictly greater, tried in the order stay, s-1,
+ * s-2; the path ends in state S-1 unless S > 1 and v(S-2) is strictly greater.
+ * path i32[B,T]: the state of every frame t < in_len[b], -1 behind; tok_start / tok_end i32[B,Lmax]: first frame of label l and
+ * one past its last, -1 for l >= tgt_len[b]; frame_logp f32[B,T]: lp_t of the path's label, 0 behind the length; score f32[B]:
+ * log-probability of the path.  An infeasible utterance (no frames, or fewer than the labels and the blanks between repeats
+ * need): score -inf, path / tok_start / tok_end -1, frame_logp 0 - the other utterances are not affected.  tgt_len = 0 is an
+ * all-blank path.  Back-pointers are 2 bits per (t, s), kept in LDS when those of an utterance fit; otherwise in `workspace`
+ * (js2t_ctc_align_workspace_bytes; contents on entry do not matter; may be NULL when that many bytes fit the kernel's LDS budget,
+ * which the call reports as an error if they do not).  No atomics, no allocation, no synchronisation: bit-reproducible, capturable. */
+int64_t js2t_ctc_align_workspace_bytes(int64_t B, int64_t T, int64_t Lmax);
+int js2t_ctc_align(const void* logits, int dt, const float* lse, const int64_t* targets, const int64_t* in_len,
+                   const int64_t* tgt_len, int32_t* path, int32_t* tok_start, int32_t* tok_end, float* frame_logp,
+                   float* score, void* workspace, int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t blank,
+                   const int32_t* row_offsets, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

@@ -101,6 +101,8 @@ def lib():
         _lib.js2t_cmvn_stats_workspace.restype = C.c_int64
         _lib.js2t_gemm_grouped_blocks.restype = C.c_int64
         _lib.js2t_gemm_grouped_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        _lib.js2t_ctc_align_workspace_bytes.restype = C.c_int64
+        _lib.js2t_ctc_align_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
         _lib.js2t_ctx_create.restype = C.c_void_p
         _lib.js2t_ctx_destroy.argtypes = [C.c_void_p]
         _lib.js2t_ctx_set.argtypes = [C.c_void_p, C.c_int32, C.c_int32]

@@ -795,6 +795,35 @@ def ctc_bwd(logits3d, lse, targets, in_len, tgt_len, alpha, nll, g_dev, scale: f
     return d
 
 
+def ctc_align_workspace_bytes(B: int, T: int, Lmax: int) -> int:
+    return int(lib().js2t_ctc_align_workspace_bytes(B, T, Lmax))
+
+
+def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "PackedRows" = None, workspace=None):
+    """CTC forced alignment (js2t_ctc_align): the best path of `targets` through the frames, inputs as for ctc_alpha.  Returns
+    (path i32[B,T] state per frame, -1 behind the length; tok_start, tok_end i32[B,Lmax] first frame / one past the last frame of every
+    label, -1 behind the target length; frame_logp f32[B,T]; score f32[B], -inf for an utterance that has no path).
+    workspace: a device buffer of >= ctc_align_workspace_bytes(B, T, Lmax) bytes to use instead of a fresh one (contents are ignored)."""
+    _dev(logits3d, lse, targets, in_len, tgt_len, workspace)
+    B, T, V, roff = _ctc_geometry(logits3d, pack)
+    Lmax = targets.shape[1]
+    dev = logits3d.device
+    need = ctc_align_workspace_bytes(B, T, Lmax)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"ctc_align: a contiguous workspace of {need} bytes expected")
+    path = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tok_start = torch.empty((B, Lmax), dtype=torch.int32, device=dev)
+    tok_end = torch.empty((B, Lmax), dtype=torch.int32, device=dev)
+    frame_logp = torch.empty((B, T), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    check(lib().js2t_ctc_align(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(path), _p(tok_start),
+                               _p(tok_end), _p(frame_logp), _p(score), _p(workspace), C.c_int64(B), C.c_int64(T), C.c_int64(V),
+                               C.c_int64(Lmax), C.c_int64(blank), roff, _stream()), "js2t_ctc_align")
+    return path, tok_start, tok_end, frame_logp, score
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the
