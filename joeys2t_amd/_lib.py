@@ -1,6 +1,10 @@
 """ctypes binding of libjoeys2t_hip.so (the C ABI declared in include/joeys2t_hip.h).
 
 There is no fallback: if the shared library is missing or a call is rejected, we raise.
+
+The header is the only place a signature or a struct layout is written down: it is parsed at import, GemmDesc / AttnDesc are built
+from its two structs and lib() sets restype / argtypes of every function it declares, so call sites pass plain Python values and a
+value of the wrong kind (a float for an int64_t) is refused before the call.
 """
 import ctypes as C
 import os
@@ -19,60 +23,66 @@ class Js2tError(RuntimeError):
     pass
 
 
+_CTYPES = {
+    "int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+    "float": C.c_float, "double": C.c_double, "js2t_stream": C.c_void_p, "js2t_ctx": C.c_void_p,
+}
+
+
+def _ctype(spelling: str, decl: str, ret: bool = False):
+    """the ctypes type of one C type spelling of the header; `decl` names the declaration in the error"""
+    t = " ".join(spelling.replace("*", " * ").split())
+    if "*" in t:
+        return C.c_char_p if ret and t == "const char *" else C.c_void_p
+    t = re.sub(r"\bconst\b", "", t).strip()
+    if ret and t == "void":
+        return None
+    if t not in _CTYPES:
+        raise Js2tError(f"{HEADER_PATH.name}: no ctypes type for '{spelling.strip()}' in '{' '.join(decl.split())}'")
+    return _CTYPES[t]
+
+
+def parse_header(text: str):
+    """(structs, functions) of the public header: {struct name: [(field, ctype)]} and {function name: (restype, [argtypes])}."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", text):
+        fields = structs[name] = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = decl.split(",")
+            base, head = re.fullmatch(r"(.*?)((?:\*\s*)*\w+)", first, flags=re.S).groups()
+            for declarator in (head, *more):
+                fields.append((declarator.replace("*", "").strip(), _ctype(base + "*" * declarator.count("*"), decl)))
+    functions = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(js2t_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        decl = f"{ret} {name}({params})"
+        params = [] if params.strip() == "void" else [re.fullmatch(r"(.*?)\w+", a.strip(), flags=re.S).group(1) for a in params.split(",")]
+        functions[name] = (_ctype(ret, decl, ret=True), [_ctype(a, decl) for a in params])
+    missed = set(re.findall(r"\b(js2t_[a-z0-9_]+)\s*\(", text)) - set(functions)
+    if missed:
+        raise Js2tError(f"{HEADER_PATH.name}: could not parse the declaration of {sorted(missed)}")
+    return structs, functions
+
+
+if not HEADER_PATH.exists():
+    raise Js2tError(f"{HEADER_PATH} is missing: the Python binding reads every struct and signature from it")
+STRUCTS, FUNCTIONS = parse_header(HEADER_PATH.read_text())
+
+
 class GemmDesc(C.Structure):
-    """Mirror of js2t_gemm_desc (include/joeys2t_hip.h)."""
-    _fields_ = [
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("batch", C.c_int32), ("batch_inner", C.c_int32),
-        ("dtype_ab", C.c_int32), ("dtype_c", C.c_int32),
-        ("trans_a", C.c_int32), ("trans_b", C.c_int32),
-        ("A", C.c_void_p), ("lda", C.c_int64), ("a_stride_o", C.c_int64), ("a_stride_i", C.c_int64),
-        ("B", C.c_void_p), ("ldb", C.c_int64), ("b_stride_o", C.c_int64), ("b_stride_i", C.c_int64),
-        ("C", C.c_void_p), ("ldc", C.c_int64), ("c_stride_o", C.c_int64), ("c_stride_i", C.c_int64),
-        ("alpha", C.c_float),
-        ("alpha_dev", C.c_void_p),
-        ("bias", C.c_void_p),
-        ("act", C.c_int32),
-        ("preact", C.c_void_p),
-        ("dropout_p", C.c_float),
-        ("rng_state", C.c_void_p),
-        ("rng_stream", C.c_uint32),
-        ("residual", C.c_void_p), ("ldr", C.c_int64), ("res_scale", C.c_float),
-        ("gate", C.c_void_p), ("ldg", C.c_int64), ("gate_scale", C.c_float),
-        ("beta", C.c_float),
-        ("conv", C.c_int32), ("conv_tin", C.c_int32), ("conv_tout", C.c_int32), ("conv_c", C.c_int32),
-        ("conv_stride", C.c_int32), ("conv_pad", C.c_int32),
-        ("split_k", C.c_int32),
-        ("a_rowsum", C.c_void_p),
-        ("ln_partial", C.c_void_p), ("ln_eps", C.c_float), ("ln_mean", C.c_void_p), ("ln_rstd", C.c_void_p), ("rs_partial", C.c_void_p),
-        ("c8", C.c_void_p), ("ldc8", C.c_int64), ("c8_state", C.c_void_p), ("c8_mul", C.c_void_p), ("c8_scale_out", C.c_void_p),
-        ("fp8_state", C.c_void_p),
-        ("dot_src", C.c_void_p), ("ld_dot", C.c_int64), ("dot_partial", C.c_void_p),
-        ("sumsq_partial", C.c_void_p),
-    ]
+    """js2t_gemm_desc (include/joeys2t_hip.h)."""
+    _fields_ = STRUCTS["js2t_gemm_desc"]
 
 
 class AttnDesc(C.Structure):
-    """Mirror of js2t_attn_desc (include/joeys2t_hip.h)."""
-    _fields_ = [
-        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("d_o", C.c_void_p),
-        ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("lse", C.c_void_p), ("delta", C.c_void_p),
-        ("mask", C.c_void_p),
-        ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("ldo", C.c_int64), ("ld_do", C.c_int64),
-        ("ld_dq", C.c_int64), ("ld_dk", C.c_int64), ("ld_dv", C.c_int64), ("mask_sb", C.c_int64), ("mask_sq", C.c_int64),
-        ("B", C.c_int32), ("H", C.c_int32), ("Tq", C.c_int32), ("Tk", C.c_int32), ("head_dim", C.c_int32),
-        ("scale", C.c_float), ("dropout_p", C.c_float),
-        ("rng_state", C.c_void_p), ("rng_stream", C.c_uint32),
-        ("rel_R", C.c_int32), ("rel_bias", C.c_void_p), ("d_rel_bias", C.c_void_p),
-        ("delta_partial", C.c_void_p), ("delta_groups", C.c_int32), ("seg", C.c_void_p), ("seg_rows", C.c_int64),
-        ("seg_keys", C.c_int32),
-    ]
+    """js2t_attn_desc (include/joeys2t_hip.h)."""
+    _fields_ = STRUCTS["js2t_attn_desc"]
 
 
-def declared_symbols(header: Path = HEADER_PATH):
+def declared_symbols():
     """Names of every function declared in the public header."""
-    text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(js2t_[a-z0-9_]+)\s*\(", text)))
+    return sorted(FUNCTIONS)
 
 
 _lib = None
@@ -92,23 +102,13 @@ def lib():
         # __graft_entry__.build() followed by smoke() in one process).  Loaded after torch, the library binds to torch's runtime:
         # one runtime, one set of streams and allocations.
         import torch  # noqa: F401
-        _lib = C.CDLL(str(LIB_PATH))
-        _lib.js2t_last_error.restype = C.c_char_p
-        _lib.js2t_colsum_partial_rows.restype = C.c_int64
-        _lib.js2t_colsum_partial_rows.argtypes = [C.c_int64]
-        _lib.js2t_sumsq_partials.restype = C.c_int64
-        _lib.js2t_sumsq_partials.argtypes = [C.c_int64]
-        _lib.js2t_cmvn_stats_workspace.restype = C.c_int64
-        _lib.js2t_gemm_grouped_blocks.restype = C.c_int64
-        _lib.js2t_gemm_grouped_blocks.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-        _lib.js2t_ctc_align_workspace_bytes.restype = C.c_int64
-        _lib.js2t_ctc_align_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
-        _lib.js2t_ctx_create.restype = C.c_void_p
-        _lib.js2t_ctx_destroy.argtypes = [C.c_void_p]
-        _lib.js2t_ctx_set.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        _lib.js2t_ctx_get.argtypes = [C.c_void_p, C.c_int32]
-        _lib.js2t_ctx_bind.restype = C.c_void_p
-        _lib.js2t_ctx_bind.argtypes = [C.c_void_p]
+        handle = C.CDLL(str(LIB_PATH))
+        for name, (restype, argtypes) in FUNCTIONS.items():  # every call converts and checks its arguments by the header's types
+            fn = getattr(handle, name, None)
+            if fn is None:
+                raise Js2tError(f"{LIB_PATH} does not export {name}, which {HEADER_PATH.name} declares: rebuild the library")
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = handle
         if "JS2T_P192" in os.environ:  # kernel-selection override for A/B measurements (see js2t_gemm_p192_mode)
             _lib.js2t_gemm_p192_mode(int(os.environ["JS2T_P192"]))
         if "JS2T_WG256" in os.environ:  # 0 / 1 / -1: the 256x128 kernel of the grouped weight gradients (js2t_gemm_wg256_mode)
@@ -152,7 +152,7 @@ class Context:
         check(lib().js2t_ctx_set(self._h, CTX_KEYS[key], int(value)), "js2t_ctx_set")
 
     def get(self, key: str) -> int:
-        return int(lib().js2t_ctx_get(self._h, CTX_KEYS[key]))
+        return lib().js2t_ctx_get(self._h, CTX_KEYS[key])
 
     def __enter__(self):
         self._prev.append(lib().js2t_ctx_bind(self._h))
@@ -173,4 +173,4 @@ class Context:
 
 def effective(key: str) -> int:
     """the value of a context key the calling thread's next launch would see (process-wide test override > bound context > default)"""
-    return int(lib().js2t_ctx_effective(CTX_KEYS[key]))
+    return lib().js2t_ctx_effective(CTX_KEYS[key])

@@ -74,8 +74,8 @@ class SumsqCollector:
     def __init__(self, grad: torch.Tensor, total: int):
         from joeys2t_amd._lib import lib
         self.grad, self.total = grad, total
-        self.per_block = int(total // max(1, lib().js2t_sumsq_partials(_C.c_int64(total)))) or 1
-        cap = 2 * int(lib().js2t_sumsq_partials(_C.c_int64(total))) + 8192
+        self.per_block = total // max(1, lib().js2t_sumsq_partials(total)) or 1
+        cap = 2 * lib().js2t_sumsq_partials(total) + 8192
         self.partial = torch.zeros((cap, ), dtype=torch.float32, device=grad.device)
         self.pos, self.covered = 0, []
         self._tables: Dict[tuple, tuple] = {}
@@ -104,17 +104,16 @@ class SumsqCollector:
             rows, pb = [], self.pos
             for lo, hi in rest:
                 rows.append([lo, hi - lo, pb])
-                pb += int(lib().js2t_sumsq_partials(_C.c_int64(hi - lo)))
+                pb += lib().js2t_sumsq_partials(hi - lo)
             if pb > self.partial.numel():
                 raise RuntimeError("SumsqCollector: partial buffer exhausted")
             table = torch.tensor(rows, dtype=torch.int64, device=self.grad.device) if rows else None
             hit = self._tables[key] = (table, len(rows), pb - self.pos, pb)
         table, n_ranges, n_blocks, n_partial = hit
         if n_ranges:
-            check(lib().js2t_sumsq_ranges(ops._p(self.grad), ops._p(table), _C.c_int32(n_ranges), _C.c_int64(n_blocks), ops._p(self.partial),
-                                          ops._stream()), "js2t_sumsq_ranges")
-        check(lib().js2t_norm_clip(ops._p(self.partial), _C.c_int64(n_partial), _C.c_float(max_norm), ops._p(out2), ops._stream()),
-              "js2t_norm_clip")
+            check(lib().js2t_sumsq_ranges(ops._p(self.grad), ops._p(table), n_ranges, n_blocks, ops._p(self.partial), ops._stream()),
+                  "js2t_sumsq_ranges")
+        check(lib().js2t_norm_clip(ops._p(self.partial), n_partial, max_norm, ops._p(out2), ops._stream()), "js2t_norm_clip")
         self.reset()
 
 
@@ -133,8 +132,7 @@ class FlatAdamW:
         self.plan_generation = 0   # bumped whenever a plan that may have been captured is replaced
         from joeys2t_amd._lib import lib
         n = store.total
-        self._partial = torch.empty((max(1, lib().js2t_sumsq_partials(_C.c_int64(n))), ), dtype=torch.float32,
-                                    device=store.device)
+        self._partial = torch.empty((max(1, lib().js2t_sumsq_partials(n)), ), dtype=torch.float32, device=store.device)
         self.norm_clip = torch.ones((2, ), dtype=torch.float32, device=store.device)  # [grad norm, clip coefficient]
         # device-resident schedule state, used when the step is replayed from a captured hipGraph
         self.lr_dev = torch.full((1, ), float(lr), dtype=torch.float32, device=store.device)
@@ -158,8 +156,8 @@ class FlatAdamW:
             if self.collector is not None and self.collector.covered:
                 self.collector.finish(max_norm, self.norm_clip)  # the products' epilogues hold most of the sum already
             else:
-                check(lib().js2t_grad_norm_clip(ops._p(st.flat_grad), _C.c_int64(st.total), _C.c_float(max_norm),
-                                                ops._p(self._partial), ops._p(self.norm_clip), ops._stream()), "js2t_grad_norm_clip")
+                check(lib().js2t_grad_norm_clip(ops._p(st.flat_grad), st.total, max_norm, ops._p(self._partial), ops._p(self.norm_clip),
+                                                ops._stream()), "js2t_grad_norm_clip")
             coef = self.norm_clip[1:2]
         if self.collector is not None:
             self.collector.reset()
@@ -173,13 +171,12 @@ class FlatAdamW:
         if plan is not None:
             # one table-driven kernel, launched twice: the 1-D parameters first (a LayerNorm fold reads the NEW gamma / beta /
             # bias), then the matrices - each block also writes the transposed bf16 image and the fold weights of its rows
-            args = (_C.c_float(g["lr"]), _C.c_float(g["betas"][0]), _C.c_float(g["betas"][1]), _C.c_float(g["eps"]),
-                    _C.c_float(g["weight_decay"]), _C.c_int64(self.t), ops._p(coef), _C.c_float(grad_scale), int(zero_grad),
+            args = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.t, ops._p(coef), grad_scale, int(zero_grad),
                     ops._p(lr_dev), ops._p(step_dev), ops._stream())
             for table, n_items, n_units in plan["launches"]:
                 check(lib().js2t_adamw_items(ops._p(st.flat), ops._p(st.flat_grad), ops._p(self.exp_avg), ops._p(self.exp_avg_sq),
-                                             ops._p(lp), ops._p(st.flat_lp_t if lp is not None else None), ops._p(table),
-                                             _C.c_int32(n_items), _C.c_int64(n_units), ops._p(plan["folds"]), *args), "js2t_adamw_items")
+                                             ops._p(lp), ops._p(st.flat_lp_t if lp is not None else None), ops._p(table), n_items, n_units,
+                                             ops._p(plan["folds"]), *args), "js2t_adamw_items")
             ops.WEIGHT_VERSION += 1
             st.dirty = lp is None and st.dirty
             if plan["left_folds"] is not None:  # folds whose matrix the kernel does not cover (wider than a unit, part of a group)
@@ -189,10 +186,8 @@ class FlatAdamW:
         # and no moment update - one launch per contiguous trainable range (the whole store when nothing is frozen)
         for lo, hi in self.update_ranges:
             check(lib().js2t_adamw(_off(st.flat, lo), _off(st.flat_grad, lo), _off(self.exp_avg, lo), _off(self.exp_avg_sq, lo),
-                                   _off(lp, lo), _C.c_int64(hi - lo), _C.c_float(g["lr"]), _C.c_float(g["betas"][0]),
-                                   _C.c_float(g["betas"][1]), _C.c_float(g["eps"]), _C.c_float(g["weight_decay"]), _C.c_int64(self.t),
-                                   ops._p(coef), _C.c_float(grad_scale), int(zero_grad), ops._p(lr_dev), ops._p(step_dev),
-                                   ops._stream()), "js2t_adamw")
+                                   _off(lp, lo), hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.t,
+                                   ops._p(coef), grad_scale, int(zero_grad), ops._p(lr_dev), ops._p(step_dev), ops._stream()), "js2t_adamw")
         ops.WEIGHT_VERSION += 1  # cached e4m3 copies of the weights (functional.FP8_FORWARD) are stale now
         st.dirty = lp is None and st.dirty
         if lp is not None and st.flat_lp_t is not None:

@@ -16,25 +16,10 @@ from joeys2t_amd._lib import Js2tError, check, lib
 from joeys2t_amd.ops import _p, dt_code
 
 
-def _bind(L):
-    if getattr(L, "_comm_bound", False):
-        return L
-    L.js2t_comm_unique_id_bytes.restype = C.c_int64
-    L.js2t_comm_unique_id.argtypes = [C.c_void_p, C.c_int64]
-    L.js2t_comm_init.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-    L.js2t_comm_allreduce_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
-    L.js2t_comm_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-    L.js2t_comm_stream.restype = C.c_void_p
-    L.js2t_comm_stream.argtypes = [C.c_void_p]
-    L.js2t_comm_destroy.argtypes = [C.c_void_p]
-    L._comm_bound = True
-    return L
-
-
 def unique_id() -> bytes:
     """A fresh ncclUniqueId (call on ONE rank, hand the bytes to all)."""
-    L = _bind(lib())
-    n = int(L.js2t_comm_unique_id_bytes())
+    L = lib()
+    n = L.js2t_comm_unique_id_bytes()
     buf = C.create_string_buffer(n)
     check(L.js2t_comm_unique_id(buf, n), "js2t_comm_unique_id")
     return buf.raw
@@ -50,7 +35,7 @@ class Communicator:
         device = torch.device(device)
         if device.type != "cuda":
             raise Js2tError("Communicator: RCCL needs a GPU (the CPU rehearsal uses torch.distributed's gloo)")
-        self._L = _bind(lib())
+        self._L = lib()
         self.rank, self.world, self.device = int(rank), int(world), device
         # rank 0 draws the id; if that fails there (librccl missing) the others must not be left waiting in the broadcast:
         # the failure travels instead of the id and every rank raises
@@ -63,13 +48,13 @@ class Communicator:
         uid = (exchange_id or _broadcast_id)(mine)
         if failed is not None:
             raise failed
-        if isinstance(uid, (bytes, bytearray)) and bytes(uid[:1]) == b"!" and len(uid) != int(self._L.js2t_comm_unique_id_bytes()):
+        if isinstance(uid, (bytes, bytearray)) and bytes(uid[:1]) == b"!" and len(uid) != self._L.js2t_comm_unique_id_bytes():
             raise Js2tError("Communicator: rank 0 could not draw an id: " + bytes(uid[1:]).decode(errors="replace"))
-        if not isinstance(uid, (bytes, bytearray)) or len(uid) != int(self._L.js2t_comm_unique_id_bytes()):
+        if not isinstance(uid, (bytes, bytearray)) or len(uid) != self._L.js2t_comm_unique_id_bytes():
             raise Js2tError("Communicator: the exchanged id is not an ncclUniqueId")
         self._h = C.c_void_p()
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        check(self._L.js2t_comm_init(C.byref(self._h), bytes(uid), len(uid), self.world, self.rank, int(idx)), "js2t_comm_init")
+        check(self._L.js2t_comm_init(C.byref(self._h), bytes(uid), len(uid), self.world, self.rank, idx), "js2t_comm_init")
         self._stream = None
 
     @classmethod
@@ -83,7 +68,7 @@ class Communicator:
     def stream(self) -> "torch.cuda.Stream":
         """The communicator's stream as a torch stream (casts into / out of a staging buffer go between the collectives)."""
         if self._stream is None:
-            self._stream = torch.cuda.ExternalStream(int(self._L.js2t_comm_stream(self._h)), device=self.device)
+            self._stream = torch.cuda.ExternalStream(self._L.js2t_comm_stream(self._h), device=self.device)
         return self._stream
 
     def all_reduce_async(self, t: torch.Tensor, average: bool = True, producer: Optional["torch.cuda.Stream"] = None):
@@ -93,15 +78,14 @@ class Communicator:
         if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.float32, torch.bfloat16):
             raise Js2tError("Communicator.all_reduce_async: contiguous float32 / bfloat16 GPU tensor")
         s = producer if producer is not None else torch.cuda.current_stream(self.device)
-        check(self._L.js2t_comm_allreduce_async(self._h, _p(t), t.numel(), dt_code(t), int(bool(average)), C.c_void_p(s.cuda_stream)),
-              "js2t_comm_allreduce_async")
+        check(self._L.js2t_comm_allreduce_async(self._h, _p(t), t.numel(), dt_code(t), bool(average), s.cuda_stream), "js2t_comm_allreduce_async")
 
     def wait(self, consumer: Optional["torch.cuda.Stream"] = None, host: bool = False):
         """`consumer` (default: the current stream) waits on the device for every collective issued so far; host=True: this thread."""
         if self._h is None:
             raise Js2tError("Communicator: closed")
         s = consumer if consumer is not None else torch.cuda.current_stream(self.device)
-        check(self._L.js2t_comm_wait(self._h, C.c_void_p(s.cuda_stream), int(bool(host))), "js2t_comm_wait")
+        check(self._L.js2t_comm_wait(self._h, s.cuda_stream, bool(host)), "js2t_comm_wait")
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -4,7 +4,6 @@ The reference transforms one NumPy spectrogram at a time on the host.  Here the 
 on the host from np.random in the reference's order (:54-68) — that is what keeps seeded runs reproducible —
 while the statistics, normalisation, masking and batch padding run on the GPU for a whole batch at once
 (js2t_cmvn_stats + js2t_feature_finalize)."""
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
@@ -98,11 +97,9 @@ def finalize_features(feat: torch.Tensor, frame_off: torch.Tensor, frames: Seque
         mean = torch.empty((U, F), dtype=torch.float32, device=dev)
         istd = torch.empty((U, F), dtype=torch.float32, device=dev)
         fill = torch.empty((U, ), dtype=torch.float32, device=dev)
-        ws = torch.empty((int(lib().js2t_cmvn_stats_workspace(C.c_int32(U), C.c_int32(F))), ), dtype=torch.float64, device=dev)
-        check(lib().js2t_cmvn_stats_ws(_p(feat), _p(frame_off), C.c_int32(U), C.c_int32(F), _p(mean), _p(istd), _p(fill),
-                                       C.c_int32(int(cmvn.norm_means)), C.c_int32(int(cmvn.norm_vars)),
-                                       C.c_int64(int(max_length) if max_length else 0), _p(ws), _stream()),
-              "js2t_cmvn_stats_ws")
+        ws = torch.empty((lib().js2t_cmvn_stats_workspace(U, F), ), dtype=torch.float64, device=dev)
+        check(lib().js2t_cmvn_stats_ws(_p(feat), _p(frame_off), U, F, _p(mean), _p(istd), _p(fill), int(cmvn.norm_means),
+                                       int(cmvn.norm_vars), int(max_length) if max_length else 0, _p(ws), _stream()), "js2t_cmvn_stats_ws")
     if specaugment is not None:
         if masks_dev is not None:  # caller-managed static int32[U,8] buffer (hipGraph replay): already drawn
             masks = masks_dev
@@ -112,9 +109,8 @@ def finalize_features(feat: torch.Tensor, frame_off: torch.Tensor, frames: Seque
         if specaugment.mask_value is not None:
             fill = torch.full((U, ), float(specaugment.mask_value), dtype=torch.float32, device=dev)
     out = torch.empty((U, Tmax, F), dtype=out_dtype, device=dev)
-    check(lib().js2t_feature_finalize_crop(_p(feat), _p(frame_off), _p(mean), _p(istd), _p(fill), _p(masks), _p(out),
-                                           ops.dt_code(out), C.c_int64(U), C.c_int64(Tmax), C.c_int32(F), C.c_float(pad_value),
-                                           _p(crop_t), _stream()), "js2t_feature_finalize")
+    check(lib().js2t_feature_finalize_crop(_p(feat), _p(frame_off), _p(mean), _p(istd), _p(fill), _p(masks), _p(out), ops.dt_code(out), U,
+                                           Tmax, F, pad_value, _p(crop_t), _stream()), "js2t_feature_finalize")
     return out, eff
 
 
@@ -123,8 +119,8 @@ def _stats(feat, frame_off, U, F, norm_means, norm_vars, max_length):
     mean = torch.empty((U, F), dtype=torch.float32, device=dev)
     istd = torch.empty((U, F), dtype=torch.float32, device=dev)
     fill = torch.empty((U, ), dtype=torch.float32, device=dev)
-    check(lib().js2t_cmvn_stats(_p(feat), _p(frame_off), C.c_int32(U), C.c_int32(F), _p(mean), _p(istd), _p(fill), C.c_int32(int(norm_means)),
-                                C.c_int32(int(norm_vars)), C.c_int64(int(max_length) if max_length else 0), _stream()), "js2t_cmvn_stats")
+    check(lib().js2t_cmvn_stats(_p(feat), _p(frame_off), U, F, _p(mean), _p(istd), _p(fill), int(norm_means), int(norm_vars),
+                                int(max_length) if max_length else 0, _stream()), "js2t_cmvn_stats")
     return mean, istd, fill
 
 
@@ -152,12 +148,12 @@ def _finalize_general(feat, frame_off, eff, cmvn, specaugment, out_dtype, pad_va
             fill = _stats(x, frame_off, U, F, False, False, max_length)[2]
     if mean is not None or masks is not None:
         nf, nt = specaugment.slots if specaugment is not None else (0, 0)
-        check(lib().js2t_feature_transform(_p(x), _p(frame_off), C.c_int32(U), C.c_int32(F), _p(mean), _p(istd), _p(fill), _p(masks),
-                                           C.c_int32(nf), C.c_int32(nt), _stream()), "js2t_feature_transform")
+        check(lib().js2t_feature_transform(_p(x), _p(frame_off), U, F, _p(mean), _p(istd), _p(fill), _p(masks), nf, nt, _stream()),
+              "js2t_feature_transform")
     mean = istd = None
     if cmvn is not None and not cmvn.before:
         mean, istd, _ = _stats(x, frame_off, U, F, cmvn.norm_means, cmvn.norm_vars, max_length)
     out = torch.empty((U, Tmax, F), dtype=out_dtype, device=dev)
-    check(lib().js2t_feature_finalize_crop(_p(x), _p(frame_off), _p(mean), _p(istd), None, None, _p(out), ops.dt_code(out), C.c_int64(U),
-                                           C.c_int64(Tmax), C.c_int32(F), C.c_float(pad_value), None, _stream()), "js2t_feature_finalize")
+    check(lib().js2t_feature_finalize_crop(_p(x), _p(frame_off), _p(mean), _p(istd), None, None, _p(out), ops.dt_code(out), U, Tmax, F,
+                                           pad_value, None, _stream()), "js2t_feature_finalize")
     return out, eff

@@ -10,7 +10,6 @@ result is pinned by the reference's known-answer test, tests/test_oracle_golden.
 25 ms window / 10 ms shift, snip_edges, dither 0, remove_dc_offset, preemphasis 0.97, Povey window, FFT size =
 next power of two, power spectrum, 80 triangular mel filters from 20 Hz to Nyquist, log(max(x, FLT_EPSILON)).
 """
-import ctypes as C
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -113,11 +112,9 @@ class FbankExtractor:
         ops._dev(wave, d_soff, d_foff)
         total = int(total_cap)
         feat = torch.empty((total, self.n_mel), dtype=torch.float32, device=self.device)
-        check(lib().js2t_fbank(_p(wave), _p(d_soff), _p(d_foff), C.c_int32(U), C.c_int64(total), _p(self.window),
-                               _p(self.tw_re), _p(self.tw_im), _p(self.mel_start), _p(self.mel_len), _p(self.mel_woff),
-                               _p(self.mel_w), _p(feat), C.c_int32(self.win_len), C.c_int32(self.shift), C.c_int32(self.n_fft),
-                               C.c_int32(self.n_mel), C.c_float(2.0**15), C.c_float(self.preemph),
-                               C.c_float(float(np.finfo(np.float32).eps)), _stream()), "js2t_fbank")
+        check(lib().js2t_fbank(_p(wave), _p(d_soff), _p(d_foff), U, total, _p(self.window), _p(self.tw_re), _p(self.tw_im),
+                               _p(self.mel_start), _p(self.mel_len), _p(self.mel_woff), _p(self.mel_w), _p(feat), self.win_len, self.shift,
+                               self.n_fft, self.n_mel, 2.0**15, self.preemph, float(np.finfo(np.float32).eps), _stream()), "js2t_fbank")
         return feat
 
 

@@ -248,7 +248,7 @@ def gemm_grouped(As, Bs, Cs, *, M, N, K, lda, ldb, ldc, split_k=1, beta=0.0, alp
 
 def grouped_blocks(M: int, N: int, count: int) -> int:
     """blocks (= sumsq_partial entries) of an un-split gemm_grouped launch"""
-    return int(lib().js2t_gemm_grouped_blocks(int(M), int(N), int(count)))
+    return lib().js2t_gemm_grouped_blocks(M, N, count)
 
 
 # ----------------------------------------------------------------------------------------- element-wise
@@ -257,21 +257,20 @@ def cast(src: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = No
     src = src.contiguous()
     if out is None:
         out = torch.empty(src.shape, dtype=dtype, device=src.device)
-    check(lib().js2t_cast(_p(src), dt_code(src), _p(out), dt_code(out), C.c_int64(src.numel()), _stream()), "js2t_cast")
+    check(lib().js2t_cast(_p(src), dt_code(src), _p(out), dt_code(out), src.numel(), _stream()), "js2t_cast")
     return out
 
 
 def axpby(x, a: float, y=None, b: float = 0.0):
     _dev(x, y)
     out = torch.empty_like(x)
-    check(lib().js2t_axpby(_p(x), C.c_float(a), _p(y), C.c_float(b), _p(out), C.c_int64(x.numel()), dt_code(x), _stream()),
-          "js2t_axpby")
+    check(lib().js2t_axpby(_p(x), a, _p(y), b, _p(out), x.numel(), dt_code(x), _stream()), "js2t_axpby")
     return out
 
 
 def transpose_groups(src, dst, table, n_groups: int, total_tiles: int):
     _dev(src, dst, table)
-    check(lib().js2t_transpose_groups(_p(src), _p(dst), _p(table), int(n_groups), C.c_int64(total_tiles), _stream()), "js2t_transpose_groups")
+    check(lib().js2t_transpose_groups(_p(src), _p(dst), _p(table), n_groups, total_tiles, _stream()), "js2t_transpose_groups")
 
 
 def glu_fwd(x: torch.Tensor, T: Optional[int] = None, valid_t: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -279,16 +278,16 @@ def glu_fwd(x: torch.Tensor, T: Optional[int] = None, valid_t: Optional[torch.Te
     _dev(x, valid_t)
     rows, c2 = x.shape[0], x.shape[1]
     y = torch.empty((rows, c2 // 2), dtype=x.dtype, device=x.device)
-    check(lib().js2t_glu_fwd_crop(_p(x), _p(y), C.c_int64(rows), C.c_int64(c2 // 2), C.c_int64(T if valid_t is not None else max(rows, 1)),
-                                  _p(valid_t), dt_code(x), _stream()), "js2t_glu_fwd")
+    check(lib().js2t_glu_fwd_crop(_p(x), _p(y), rows, c2 // 2, T if valid_t is not None else max(rows, 1), _p(valid_t), dt_code(x),
+                                  _stream()), "js2t_glu_fwd")
     return y
 
 
 def glu_bwd(x: torch.Tensor, dy: torch.Tensor, T: Optional[int] = None, valid_t: Optional[torch.Tensor] = None) -> torch.Tensor:
     _dev(x, dy, valid_t)
     dx = torch.empty_like(x)
-    check(lib().js2t_glu_bwd_crop(_p(x), _p(dy), _p(dx), C.c_int64(x.shape[0]), C.c_int64(x.shape[1] // 2),
-                                  C.c_int64(T if valid_t is not None else max(x.shape[0], 1)), _p(valid_t), dt_code(x), _stream()), "js2t_glu_bwd")
+    check(lib().js2t_glu_bwd_crop(_p(x), _p(dy), _p(dx), x.shape[0], x.shape[1] // 2, T if valid_t is not None else max(x.shape[0], 1),
+                                  _p(valid_t), dt_code(x), _stream()), "js2t_glu_bwd")
     return dx
 
 
@@ -296,9 +295,8 @@ def add_pe_dropout(x, pe, extra, p, rng: Optional[DropoutRng], site: int):
     _dev(x, pe, extra)
     B, T, D = x.shape
     y = torch.empty_like(x)
-    check(lib().js2t_add_pe_dropout(_p(x), _p(pe), _p(extra), _p(y), C.c_int64(B), C.c_int64(T), C.c_int64(D), dt_code(x),
-                                    C.c_float(p), _p(rng.state) if p > 0 else None, C.c_uint32(site), _stream()),
-          "js2t_add_pe_dropout")
+    check(lib().js2t_add_pe_dropout(_p(x), _p(pe), _p(extra), _p(y), B, T, D, dt_code(x), p, _p(rng.state) if p > 0 else None, site,
+                                    _stream()), "js2t_add_pe_dropout")
     return y
 
 
@@ -308,16 +306,14 @@ def dropout_bwd(dy, p, rng: DropoutRng, site: int):
     cols = dy.shape[-1]
     rows = dy.numel() // cols
     dx = torch.empty_like(dy)
-    check(lib().js2t_dropout_bwd(_p(dy), _p(dx), C.c_int64(rows), C.c_int64(cols), dt_code(dy), C.c_float(p),
-                                 _p(rng.state), C.c_uint32(site), _stream()), "js2t_dropout_bwd")
+    check(lib().js2t_dropout_bwd(_p(dy), _p(dx), rows, cols, dt_code(dy), p, _p(rng.state), site, _stream()), "js2t_dropout_bwd")
     return dx
 
 
 def act_bwd(dh, z, act: str, scale: float = 1.0):
     _dev(dh, z)
     dz = torch.empty_like(dh)
-    check(lib().js2t_act_bwd(_p(dh), _p(z), _p(dz), C.c_int64(dh.numel()), ACT_CODES[act], dt_code(dh), C.c_float(scale),
-                             _stream()), "js2t_act_bwd")
+    check(lib().js2t_act_bwd(_p(dh), _p(z), _p(dz), dh.numel(), ACT_CODES[act], dt_code(dh), scale, _stream()), "js2t_act_bwd")
     return dz
 
 
@@ -326,8 +322,7 @@ def embed_fwd(ids, table, scale: float, out_dtype):
     ids = ids.contiguous()
     D, V = table.shape[1], table.shape[0]
     out = torch.empty((*ids.shape, D), dtype=out_dtype, device=table.device)
-    check(lib().js2t_embed_fwd(_p(ids), _p(table), dt_code(table), _p(out), dt_code(out), C.c_int64(ids.numel()),
-                               C.c_int64(D), C.c_int64(V), C.c_float(scale), _stream()), "js2t_embed_fwd")
+    check(lib().js2t_embed_fwd(_p(ids), _p(table), dt_code(table), _p(out), dt_code(out), ids.numel(), D, V, scale, _stream()), "js2t_embed_fwd")
     return out
 
 
@@ -336,9 +331,8 @@ def embed_bwd(ids, dout, vocab: int, scale: float, pad_idx: int, out: Optional[t
     ids, dout = ids.contiguous(), dout.contiguous()
     D = dout.shape[-1]
     dtable = out if out is not None else torch.zeros((vocab, D), dtype=torch.float32, device=dout.device)
-    check(lib().js2t_embed_bwd(_p(ids), _p(dout), dt_code(dout), _p(dtable), C.c_int64(ids.numel()), C.c_int64(D),
-                               C.c_int64(vocab), C.c_float(scale), C.c_int64(-1 if pad_idx is None else pad_idx), _stream()),
-          "js2t_embed_bwd")
+    check(lib().js2t_embed_bwd(_p(ids), _p(dout), dt_code(dout), _p(dtable), ids.numel(), D, vocab, scale,
+                               -1 if pad_idx is None else pad_idx, _stream()), "js2t_embed_bwd")
     return dtable
 
 
@@ -350,8 +344,7 @@ def colsum(x2d: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bo
         accumulate = False
     nparts = lib().js2t_colsum_partial_rows(rows)
     partial = torch.empty((max(nparts, 1) * cols,), dtype=torch.float32, device=x2d.device)
-    check(lib().js2t_colsum(_p(x2d), dt_code(x2d), _p(out), _p(partial), C.c_int64(rows), C.c_int64(cols), int(accumulate),
-                            _stream()), "js2t_colsum")
+    check(lib().js2t_colsum(_p(x2d), dt_code(x2d), _p(out), _p(partial), rows, cols, int(accumulate), _stream()), "js2t_colsum")
     return out
 
 
@@ -359,8 +352,7 @@ def conv_weight_pack(w: torch.Tensor, dtype) -> torch.Tensor:
     _dev(w)
     cout, cin, k = w.shape
     wp = torch.empty((cout, k * cin), dtype=dtype, device=w.device)
-    check(lib().js2t_conv_weight_pack(_p(w.contiguous()), _p(wp), dt_code(wp), C.c_int64(cout), C.c_int64(cin), C.c_int64(k),
-                                      _stream()), "js2t_conv_weight_pack")
+    check(lib().js2t_conv_weight_pack(_p(w.contiguous()), _p(wp), dt_code(wp), cout, cin, k, _stream()), "js2t_conv_weight_pack")
     return wp
 
 
@@ -369,8 +361,7 @@ def conv_weight_unpack_grad(dwp_t: torch.Tensor, cout: int, cin: int, k: int, ou
     _dev(dwp_t, out)
     acc = out is not None
     dw = out if acc else torch.empty((cout, cin, k), dtype=torch.float32, device=dwp_t.device)
-    check(lib().js2t_conv_weight_unpack_grad(_p(dwp_t), _p(dw), C.c_int64(cout), C.c_int64(cin), C.c_int64(k), int(acc),
-                                             _stream()), "js2t_conv_weight_unpack_grad")
+    check(lib().js2t_conv_weight_unpack_grad(_p(dwp_t), _p(dw), cout, cin, k, int(acc), _stream()), "js2t_conv_weight_unpack_grad")
     return dw
 
 
@@ -380,16 +371,14 @@ def im2col(x3d, K, stride, pad, tout):
     B, tin, Cc = x3d.shape
     x3d = x3d.contiguous()
     col = torch.empty((B * tout, K * Cc), dtype=x3d.dtype, device=x3d.device)
-    check(lib().js2t_im2col(_p(x3d), _p(col), C.c_int64(B), C.c_int64(tin), C.c_int64(tout), C.c_int64(Cc), C.c_int64(K),
-                            C.c_int64(stride), C.c_int64(pad), dt_code(x3d), _stream()), "js2t_im2col")
+    check(lib().js2t_im2col(_p(x3d), _p(col), B, tin, tout, Cc, K, stride, pad, dt_code(x3d), _stream()), "js2t_im2col")
     return col
 
 
 def col2im(dcol, B, tin, tout, Cc, K, stride, pad):
     _dev(dcol)
     dx = torch.empty((B, tin, Cc), dtype=dcol.dtype, device=dcol.device)
-    check(lib().js2t_col2im(_p(dcol), _p(dx), C.c_int64(B), C.c_int64(tin), C.c_int64(tout), C.c_int64(Cc), C.c_int64(K),
-                            C.c_int64(stride), C.c_int64(pad), dt_code(dcol), _stream()), "js2t_col2im")
+    check(lib().js2t_col2im(_p(dcol), _p(dx), B, tin, tout, Cc, K, stride, pad, dt_code(dcol), _stream()), "js2t_col2im")
     return dx
 
 
@@ -400,8 +389,8 @@ def subsample_lengths_mask(lengths: torch.Tensor, t_out: int, kernel_sizes: Sequ
     out_len = torch.empty((B,), dtype=torch.int64, device=lengths.device)
     mask = torch.empty((B, 1, t_out), dtype=torch.bool, device=lengths.device)
     ks = (C.c_int32 * len(kernel_sizes))(*kernel_sizes)
-    check(lib().js2t_subsample_lengths_mask(_p(lengths), _p(out_len), _p(mask), C.c_int64(B), C.c_int64(t_out), ks,
-                                            C.c_int32(len(kernel_sizes)), _stream()), "js2t_subsample_lengths_mask")
+    check(lib().js2t_subsample_lengths_mask(_p(lengths), _p(out_len), _p(mask), B, t_out, ks, len(kernel_sizes), _stream()),
+          "js2t_subsample_lengths_mask")
     return out_len, mask
 
 
@@ -413,8 +402,8 @@ def layernorm_fwd(x, gamma, beta, eps: float):
     y = torch.empty_like(x)
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    check(lib().js2t_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), C.c_int64(rows), C.c_int64(D),
-                                   C.c_float(eps), dt_code(x), _stream()), "js2t_layernorm_fwd")
+    check(lib().js2t_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, eps, dt_code(x), _stream()),
+          "js2t_layernorm_fwd")
     return y, mean, rstd
 
 
@@ -429,8 +418,8 @@ def layernorm_fwd_fp8(x, gamma, beta, eps: float, state: torch.Tensor, mul: Opti
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
     scale = torch.empty((1, ), dtype=torch.float32, device=x.device)
-    check(lib().js2t_layernorm_fwd_fp8(_p(x), _p(gamma), _p(beta), _p(y), _p(y8), _p(state), _p(mul), _p(scale), _p(mean), _p(rstd),
-                                       C.c_int64(rows), C.c_int64(D), C.c_float(eps), dt_code(x), _stream()), "js2t_layernorm_fwd_fp8")
+    check(lib().js2t_layernorm_fwd_fp8(_p(x), _p(gamma), _p(beta), _p(y), _p(y8), _p(state), _p(mul), _p(scale), _p(mean), _p(rstd), rows,
+                                       D, eps, dt_code(x), _stream()), "js2t_layernorm_fwd_fp8")
     return y, mean, rstd, y8, scale
 
 
@@ -484,8 +473,7 @@ class GradCopies:
                 self.captured_rows = self.n_rows
             elif self.captured_rows is not None and self.n_rows != self.captured_rows:
                 raise Js2tError("GradCopies: slots were registered after a hipGraph captured fold(); re-capture the step")
-            check(lib().js2t_fold_copies(_p(self.ws), _p(self.table), C.c_int32(self.n_rows), C.c_int32(self.COPIES),
-                                         C.c_int64(self.stride), _stream()), "js2t_fold_copies")
+            check(lib().js2t_fold_copies(_p(self.ws), _p(self.table), self.n_rows, self.COPIES, self.stride, _stream()), "js2t_fold_copies")
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, need_param_grads=True, add=None, add_scale=1.0, grad_out=None, drop=None,
@@ -521,12 +509,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, need_param_grads=True, add=None, add
         copies = 1
     p_drop, rng, site = drop if drop is not None else (0.0, None, 0)
     dxd = torch.empty_like(x) if drop is not None else None
-    check(lib().js2t_layernorm_bwd_fused(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(add), C.c_float(add_scale), _p(acc_g),
-                                         _p(acc_b), _p(partial), int(grad_out is not None and need_param_grads), C.c_int64(rows),
-                                         C.c_int64(D), dt_code(x), _p(dxd), C.c_float(p_drop), None if rng is None else _p(rng.state),
-                                         C.c_uint32(site & 0xFFFFFFFF), C.c_int32(copies), C.c_int64(stride), _p(beta) if n_out is not None else None,
-                                         _p(n_out), _stream()),
-          "js2t_layernorm_bwd_fused")
+    check(lib().js2t_layernorm_bwd_fused(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(add), add_scale, _p(acc_g), _p(acc_b),
+                                         _p(partial), int(grad_out is not None and need_param_grads), rows, D, dt_code(x), _p(dxd), p_drop,
+                                         None if rng is None else _p(rng.state), site & 0xFFFFFFFF, copies, stride,
+                                         _p(beta) if n_out is not None else None, _p(n_out), _stream()), "js2t_layernorm_bwd_fused")
     if drop is None:
         return dx, dgamma, dbeta
     return dx, dgamma, dbeta, dxd
@@ -536,7 +522,7 @@ def fold_ln_weights(table: torch.Tensor, n_entries: int, max_rows: int):
     """(Re)derive the centred, gamma-scaled bf16 weights and the beta-absorbing biases of every LayerNorm fold
     (js2t_fold_ln_weights; table int64[n, 8] on the device)."""
     _dev(table)
-    check(lib().js2t_fold_ln_weights(_p(table), C.c_int32(n_entries), C.c_int32(max_rows), _stream()), "js2t_fold_ln_weights")
+    check(lib().js2t_fold_ln_weights(_p(table), n_entries, max_rows, _stream()), "js2t_fold_ln_weights")
 
 
 def layernorm_bwd_supports_dropout(x) -> bool:
@@ -552,8 +538,7 @@ def dwconv_outer_fwd(x3d: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Te
     L, N, Cc = x3d.shape
     x3d = x3d.contiguous()
     y = torch.empty_like(x3d)
-    check(lib().js2t_dwconv_outer_fwd(_p(x3d), _p(w), _p(bias), _p(y), C.c_int64(L), C.c_int64(N), C.c_int64(Cc), int(w.shape[1]),
-                                      dt_code(x3d), _stream()), "js2t_dwconv_outer_fwd")
+    check(lib().js2t_dwconv_outer_fwd(_p(x3d), _p(w), _p(bias), _p(y), L, N, Cc, w.shape[1], dt_code(x3d), _stream()), "js2t_dwconv_outer_fwd")
     return y
 
 
@@ -564,8 +549,8 @@ def dwconv_outer_bwd(dy3d, x3d, w, need_dx=True, dw_out: Optional[torch.Tensor] 
     dy3d = dy3d.contiguous()
     dx = torch.empty_like(x3d) if need_dx else None
     dw = dw_out if dw_out is not None else torch.zeros((Cc, w.shape[1]), dtype=torch.float32, device=x3d.device)
-    check(lib().js2t_dwconv_outer_bwd(_p(dy3d), _p(x3d), _p(w), _p(dx), _p(dw), C.c_int64(L), C.c_int64(N), C.c_int64(Cc),
-                                      int(w.shape[1]), dt_code(x3d), _stream()), "js2t_dwconv_outer_bwd")
+    check(lib().js2t_dwconv_outer_bwd(_p(dy3d), _p(x3d), _p(w), _p(dx), _p(dw), L, N, Cc, w.shape[1], dt_code(x3d), _stream()),
+          "js2t_dwconv_outer_bwd")
     return dx, (None if dw_out is not None else dw)
 
 
@@ -578,9 +563,8 @@ def bn_act_fwd(x2d, gamma, beta, running_mean, running_var, eps: float, momentum
     mean = torch.empty((Cc,), dtype=torch.float32, device=x2d.device)
     invstd = torch.empty_like(mean)
     ws = torch.empty((2 * Cc,), dtype=torch.float32, device=x2d.device)
-    check(lib().js2t_bn_act_fwd(_p(x2d), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(mean), _p(invstd), _p(y), _p(ws),
-                                C.c_int64(rows), C.c_int64(Cc), C.c_float(eps), C.c_float(momentum), int(train), ACT_CODES[act],
-                                dt_code(x2d), _stream()), "js2t_bn_act_fwd")
+    check(lib().js2t_bn_act_fwd(_p(x2d), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(mean), _p(invstd), _p(y), _p(ws), rows,
+                                Cc, eps, momentum, int(train), ACT_CODES[act], dt_code(x2d), _stream()), "js2t_bn_act_fwd")
     return y, mean, invstd
 
 
@@ -596,8 +580,8 @@ def bn_act_bwd(dy2d, x2d, gamma, beta, mean, invstd, train: bool, act: Optional[
         dg = torch.zeros((Cc,), dtype=torch.float32, device=x2d.device)
         db = torch.zeros_like(dg)
     ws = torch.empty((2 * Cc,), dtype=torch.float32, device=x2d.device)
-    check(lib().js2t_bn_act_bwd(_p(dy2d), _p(x2d), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dx), _p(dg), _p(db), _p(ws),
-                                C.c_int64(rows), C.c_int64(Cc), int(train), ACT_CODES[act], dt_code(x2d), _stream()), "js2t_bn_act_bwd")
+    check(lib().js2t_bn_act_bwd(_p(dy2d), _p(x2d), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dx), _p(dg), _p(db), _p(ws), rows, Cc,
+                                int(train), ACT_CODES[act], dt_code(x2d), _stream()), "js2t_bn_act_bwd")
     return (dx, None, None) if grad_out is not None else (dx, dg, db)
 
 
@@ -616,17 +600,15 @@ def softmax_fwd(S, mask, B, H, Tq, Tk, ld, p, rng: Optional[DropoutRng], site: i
         mask_sb = 0 if mask.shape[0] == 1 else mask.shape[1] * Tk
         if mask.shape[0] not in (1, B):
             raise Js2tError(f"softmax: mask batch dim {mask.shape[0]} != 1 or {B}")
-    check(lib().js2t_softmax_fwd(_p(S), _p(mask), _p(P), _p(Pd), C.c_int64(B), C.c_int64(H), C.c_int64(Tq), C.c_int64(Tk),
-                                 C.c_int64(ld), C.c_int64(mask_sb), C.c_int64(mask_sq), dt_code(S), C.c_float(p),
-                                 _p(rng.state) if p > 0 else None, C.c_uint32(site), _stream()), "js2t_softmax_fwd")
+    check(lib().js2t_softmax_fwd(_p(S), _p(mask), _p(P), _p(Pd), B, H, Tq, Tk, ld, mask_sb, mask_sq, dt_code(S), p,
+                                 _p(rng.state) if p > 0 else None, site, _stream()), "js2t_softmax_fwd")
     return P, Pd
 
 
 def softmax_bwd(P, dPd, Z, Tq, Tk, ld, p, rng: Optional[DropoutRng], site: int):
     _dev(P, dPd)
     dS = torch.empty_like(P)
-    check(lib().js2t_softmax_bwd(_p(P), _p(dPd), _p(dS), C.c_int64(Z), C.c_int64(Tq), C.c_int64(Tk), C.c_int64(ld),
-                                 dt_code(P), C.c_float(p), _p(rng.state) if p > 0 else None, C.c_uint32(site), _stream()),
+    check(lib().js2t_softmax_bwd(_p(P), _p(dPd), _p(dS), Z, Tq, Tk, ld, dt_code(P), p, _p(rng.state) if p > 0 else None, site, _stream()),
           "js2t_softmax_bwd")
     return dS
 
@@ -634,8 +616,7 @@ def softmax_bwd(P, dPd, Z, Tq, Tk, ld, p, rng: Optional[DropoutRng], site: int):
 def attn_head_mean(P, B, H, Tq, Tk, ld):
     _dev(P)
     out = torch.empty((B, Tq, Tk), dtype=torch.float32, device=P.device)
-    check(lib().js2t_attn_head_mean(_p(P), _p(out), C.c_int64(B), C.c_int64(H), C.c_int64(Tq), C.c_int64(Tk), C.c_int64(ld),
-                                    dt_code(P), _stream()), "js2t_attn_head_mean")
+    check(lib().js2t_attn_head_mean(_p(P), _p(out), B, H, Tq, Tk, ld, dt_code(P), _stream()), "js2t_attn_head_mean")
     return out
 
 
@@ -643,8 +624,7 @@ def rel_bias_add(S, rel_bias, B, H, Tq, Tk, ld):
     """S[b,h,q,k] += rel_bias[h, clamp(k - q)] in place (js2t_rel_bias_add; the materialised attention path)."""
     _dev(S, rel_bias)
     R = (rel_bias.shape[1] - 1) // 2
-    check(lib().js2t_rel_bias_add(_p(S), _p(rel_bias), C.c_int64(B), C.c_int64(H), C.c_int64(Tq), C.c_int64(Tk), C.c_int64(ld),
-                                  C.c_int32(R), dt_code(S), _stream()), "js2t_rel_bias_add")
+    check(lib().js2t_rel_bias_add(_p(S), _p(rel_bias), B, H, Tq, Tk, ld, R, dt_code(S), _stream()), "js2t_rel_bias_add")
     return S
 
 
@@ -652,8 +632,7 @@ def rel_bias_grad(dS, d_rel_bias, B, H, Tq, Tk, ld):
     """d_rel_bias += the per-(head, clipped distance) sums of dS (js2t_rel_bias_grad)."""
     _dev(dS, d_rel_bias)
     R = (d_rel_bias.shape[1] - 1) // 2
-    check(lib().js2t_rel_bias_grad(_p(dS), _p(d_rel_bias), C.c_int64(B), C.c_int64(H), C.c_int64(Tq), C.c_int64(Tk), C.c_int64(ld),
-                                   C.c_int32(R), dt_code(dS), _stream()), "js2t_rel_bias_grad")
+    check(lib().js2t_rel_bias_grad(_p(dS), _p(d_rel_bias), B, H, Tq, Tk, ld, R, dt_code(dS), _stream()), "js2t_rel_bias_grad")
 
 
 def round_up(x: int, m: int) -> int:
@@ -666,7 +645,7 @@ def row_lse(x2d: torch.Tensor, want_argmax: bool = False):
     rows, V = x2d.shape
     lse = torch.empty((rows,), dtype=torch.float32, device=x2d.device)
     am = torch.empty((rows,), dtype=torch.int64, device=x2d.device) if want_argmax else None
-    check(lib().js2t_row_lse(_p(x2d), _p(lse), _p(am), C.c_int64(rows), C.c_int64(V), dt_code(x2d), _stream()), "js2t_row_lse")
+    check(lib().js2t_row_lse(_p(x2d), _p(lse), _p(am), rows, V, dt_code(x2d), _stream()), "js2t_row_lse")
     return lse, am
 
 
@@ -678,8 +657,7 @@ def ctc_collapse(best: torch.Tensor, in_len: torch.Tensor, blank: int, pad: int)
     in_len = in_len.to(torch.int64).contiguous()
     out = torch.empty((B, T), dtype=torch.int64, device=best.device)
     n = torch.empty((B,), dtype=torch.int64, device=best.device)
-    check(lib().js2t_ctc_collapse(_p(best), _p(in_len), _p(out), _p(n), C.c_int64(B), C.c_int64(T), C.c_int64(blank), C.c_int64(pad),
-                                  _stream()), "js2t_ctc_collapse")
+    check(lib().js2t_ctc_collapse(_p(best), _p(in_len), _p(out), _p(n), B, T, blank, pad, _stream()), "js2t_ctc_collapse")
     return out, n
 
 
@@ -689,8 +667,7 @@ def log_softmax(x: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
     V = x.shape[-1]
     rows = x.numel() // V
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    check(lib().js2t_log_softmax(_p(x), dt_code(x), _p(y), dt_code(y), C.c_int64(rows), C.c_int64(V), _stream()),
-          "js2t_log_softmax")
+    check(lib().js2t_log_softmax(_p(x), dt_code(x), _p(y), dt_code(y), rows, V, _stream()), "js2t_log_softmax")
     return y
 
 
@@ -700,8 +677,8 @@ def train_stats(stats6, total, nll, ctc, n_correct, inv_norm: float, nseqs: floa
     assert stats6.dtype == torch.float64 and stats6.numel() == 6 and total.dtype == torch.float32
     assert n_correct is None or n_correct.dtype == torch.int64
     norm = torch.empty((), dtype=torch.float32, device=total.device)
-    check(lib().js2t_train_stats(_p(stats6), _p(total), _p(nll), _p(ctc), _p(n_correct), C.c_double(inv_norm), C.c_double(nseqs),
-                                 C.c_double(ntokens), _p(norm), _stream()), "js2t_train_stats")
+    check(lib().js2t_train_stats(_p(stats6), _p(total), _p(nll), _p(ctc), _p(n_correct), inv_norm, nseqs, ntokens, _p(norm), _stream()),
+          "js2t_train_stats")
     return norm
 
 
@@ -723,7 +700,7 @@ class LinComb2Fn(torch.autograd.Function):
 def sum_f32(x: torch.Tensor) -> torch.Tensor:
     _dev(x)
     out = torch.empty((), dtype=torch.float32, device=x.device)
-    check(lib().js2t_sum_f32(_p(x), C.c_int64(x.numel()), _p(out), _stream()), "js2t_sum_f32")
+    check(lib().js2t_sum_f32(_p(x), x.numel(), _p(out), _stream()), "js2t_sum_f32")
     return out
 
 
@@ -734,9 +711,8 @@ def xent_fwd(logits2d, trg1d, pad_idx: int, smoothing: float):
     loss_rows = torch.empty((rows,), dtype=torch.float32, device=dev)
     correct_rows = torch.empty((rows,), dtype=torch.float32, device=dev)
     lse = torch.empty((rows,), dtype=torch.float32, device=dev)
-    check(lib().js2t_xent_fwd(_p(logits2d), dt_code(logits2d), _p(trg1d), _p(loss_rows), _p(correct_rows), _p(lse),
-                              C.c_int64(rows), C.c_int64(V), C.c_int64(pad_idx), C.c_float(smoothing), _stream()),
-          "js2t_xent_fwd")
+    check(lib().js2t_xent_fwd(_p(logits2d), dt_code(logits2d), _p(trg1d), _p(loss_rows), _p(correct_rows), _p(lse), rows, V, pad_idx,
+                              smoothing, _stream()), "js2t_xent_fwd")
     return loss_rows, correct_rows, lse
 
 
@@ -745,9 +721,8 @@ def xent_bwd(logits2d, trg1d, lse, g_dev, scale: float, pad_idx: int, smoothing:
     _dev(logits2d, trg1d, lse, g_dev)
     rows, V = logits2d.shape
     d = torch.empty(logits2d.shape, dtype=out_dtype or logits2d.dtype, device=logits2d.device)
-    check(lib().js2t_xent_bwd_as(_p(logits2d), dt_code(logits2d), _p(trg1d), _p(lse), _p(g_dev), C.c_float(scale), _p(d), dt_code(d),
-                                 C.c_int64(rows), C.c_int64(V), C.c_int64(pad_idx), C.c_float(smoothing), _stream()),
-          "js2t_xent_bwd_as")
+    check(lib().js2t_xent_bwd_as(_p(logits2d), dt_code(logits2d), _p(trg1d), _p(lse), _p(g_dev), scale, _p(d), dt_code(d), rows, V, pad_idx,
+                                 smoothing, _stream()), "js2t_xent_bwd_as")
     return d
 
 
@@ -759,7 +734,7 @@ def _ctc_geometry(logits, pack):
     if logits.dim() != 2 or logits.shape[0] != pack.rows or not logits.is_contiguous():
         raise Js2tError(f"CTC over packed rows: contiguous [{pack.rows}, V] logits expected, got {tuple(logits.shape)}")
     _dev(pack.seg)
-    return pack.B, pack.T, logits.shape[1], C.c_void_p(pack.seg.data_ptr())
+    return pack.B, pack.T, logits.shape[1], _p(pack.seg)
 
 
 def ctc_alpha(logits3d, lse, targets, in_len, tgt_len, blank: int, zero_infinity: bool, with_beta: bool = False, pack: "PackedRows" = None):
@@ -773,9 +748,8 @@ def ctc_alpha(logits3d, lse, targets, in_len, tgt_len, blank: int, zero_infinity
     beta = torch.empty_like(alpha) if with_beta else None
     nll = torch.empty((B,), dtype=torch.float32, device=dev)
     loss_rows = torch.empty((B,), dtype=torch.float32, device=dev)
-    check(lib().js2t_ctc_alpha(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(alpha), _p(beta),
-                               _p(nll), _p(loss_rows), C.c_int64(B), C.c_int64(T), C.c_int64(V), C.c_int64(Lmax),
-                               C.c_int64(blank), int(zero_infinity), roff, _stream()), "js2t_ctc_alpha")
+    check(lib().js2t_ctc_alpha(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(alpha), _p(beta), _p(nll),
+                               _p(loss_rows), B, T, V, Lmax, blank, int(zero_infinity), roff, _stream()), "js2t_ctc_alpha")
     return alpha, nll, loss_rows, beta
 
 
@@ -788,15 +762,14 @@ def ctc_bwd(logits3d, lse, targets, in_len, tgt_len, alpha, nll, g_dev, scale: f
     if beta is None:
         beta = torch.empty_like(alpha)
     d = torch.empty_like(logits3d)
-    check(lib().js2t_ctc_bwd(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(alpha),
-                             _p(beta), _p(nll), _p(g_dev), C.c_float(scale), _p(d), C.c_int64(B), C.c_int64(T), C.c_int64(V),
-                             C.c_int64(Lmax), C.c_int64(blank), int(zero_infinity), int(ready), roff,
-                             C.c_int64(0 if pack is None else pack.rows), _stream()), "js2t_ctc_bwd")
+    check(lib().js2t_ctc_bwd(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(alpha), _p(beta), _p(nll),
+                             _p(g_dev), scale, _p(d), B, T, V, Lmax, blank, int(zero_infinity), int(ready), roff,
+                             0 if pack is None else pack.rows, _stream()), "js2t_ctc_bwd")
     return d
 
 
 def ctc_align_workspace_bytes(B: int, T: int, Lmax: int) -> int:
-    return int(lib().js2t_ctc_align_workspace_bytes(B, T, Lmax))
+    return lib().js2t_ctc_align_workspace_bytes(B, T, Lmax)
 
 
 def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "PackedRows" = None, workspace=None):
@@ -819,8 +792,7 @@ def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "Packed
     frame_logp = torch.empty((B, T), dtype=torch.float32, device=dev)
     score = torch.empty((B,), dtype=torch.float32, device=dev)
     check(lib().js2t_ctc_align(_p(logits3d), dt_code(logits3d), _p(lse), _p(targets), _p(in_len), _p(tgt_len), _p(path), _p(tok_start),
-                               _p(tok_end), _p(frame_logp), _p(score), _p(workspace), C.c_int64(B), C.c_int64(T), C.c_int64(V),
-                               C.c_int64(Lmax), C.c_int64(blank), roff, _stream()), "js2t_ctc_align")
+                               _p(tok_end), _p(frame_logp), _p(score), _p(workspace), B, T, V, Lmax, blank, roff, _stream()), "js2t_ctc_align")
     return path, tok_start, tok_end, frame_logp, score
 
 
@@ -831,9 +803,9 @@ def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, len
     _dev(q2d, k_view, v_view, idx, key_mask, len_dev)
     rows = q2d.shape[0]
     out = torch.empty((rows, H * dh), dtype=q2d.dtype, device=q2d.device)
-    check(lib().js2t_attn_decode(_p(q2d), C.c_int64(q2d.stride(0)), _p(k_view), _p(v_view), C.c_int64(ldkv), _p(idx), int(idx_ld), int(Tmax),
-                                 int(length), _p(len_dev), _p(key_mask), _p(out), C.c_int64(out.stride(0)), int(rows), int(H), int(dh),
-                                 C.c_float(1.0 / math.sqrt(dh)), int(group), dt_code(q2d), _stream()), "js2t_attn_decode")
+    check(lib().js2t_attn_decode(_p(q2d), q2d.stride(0), _p(k_view), _p(v_view), ldkv, _p(idx), idx_ld, Tmax, length, _p(len_dev),
+                                 _p(key_mask), _p(out), out.stride(0), rows, H, dh, 1.0 / math.sqrt(dh), group, dt_code(q2d), _stream()),
+          "js2t_attn_decode")
     return out
 
 
@@ -852,9 +824,8 @@ def quantize_fp8(x: torch.Tensor, mul: Optional[torch.Tensor] = None):
     y = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
     amax = torch.empty((1, ), dtype=torch.float32, device=x.device)
     scale = torch.empty((1, ), dtype=torch.float32, device=x.device)
-    check(lib().js2t_absmax(_p(x), dt_code(x), C.c_int64(x.numel()), _p(amax), _stream()), "js2t_absmax")
-    check(lib().js2t_quantize_fp8(_p(x), dt_code(x), _p(y), C.c_int64(x.numel()), _p(amax), _p(mul), _p(scale), _stream()),
-          "js2t_quantize_fp8")
+    check(lib().js2t_absmax(_p(x), dt_code(x), x.numel(), _p(amax), _stream()), "js2t_absmax")
+    check(lib().js2t_quantize_fp8(_p(x), dt_code(x), _p(y), x.numel(), _p(amax), _p(mul), _p(scale), _stream()), "js2t_quantize_fp8")
     return y, scale
 
 
@@ -866,7 +837,7 @@ def quantize_fp8_delayed(x: torch.Tensor, state: torch.Tensor, mul: Optional[tor
         raise Js2tError("quantize_fp8_delayed: contiguous float32 / bfloat16 input")
     y = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
     scale = torch.empty((1, ), dtype=torch.float32, device=x.device)
-    check(lib().js2t_quantize_fp8_delayed(_p(x), dt_code(x), _p(y), C.c_int64(x.numel()), _p(state), _p(mul), _p(scale), _stream()),
+    check(lib().js2t_quantize_fp8_delayed(_p(x), dt_code(x), _p(y), x.numel(), _p(state), _p(mul), _p(scale), _stream()),
           "js2t_quantize_fp8_delayed")
     return y, scale
 
@@ -875,7 +846,7 @@ def new_fp8_state(x: torch.Tensor) -> torch.Tensor:
     """Calibrate a delayed-scaling state on x: {max|x| / 448, 0, 0, 0}."""
     _dev(x)
     amax = torch.empty((1, ), dtype=torch.float32, device=x.device)
-    check(lib().js2t_absmax(_p(x), dt_code(x), C.c_int64(x.numel()), _p(amax), _stream()), "js2t_absmax")
+    check(lib().js2t_absmax(_p(x), dt_code(x), x.numel(), _p(amax), _stream()), "js2t_absmax")
     state = torch.zeros((4, ), dtype=torch.float32, device=x.device)
     state[0:1] = amax / 448.0
     return state
@@ -890,8 +861,7 @@ def rep_penalty(log_probs: torch.Tensor, tokens: torch.Tensor, penalty: float):
     rows, V = log_probs.shape
     if tokens.shape[0] != rows:
         raise Js2tError(f"rep_penalty: {tokens.shape[0]} token rows for {rows} score rows")
-    check(lib().js2t_rep_penalty(_p(log_probs), _p(tokens), C.c_int64(rows), C.c_int64(V), C.c_int64(tokens.shape[1]),
-                                 C.c_float(penalty), _stream()), "js2t_rep_penalty")
+    check(lib().js2t_rep_penalty(_p(log_probs), _p(tokens), rows, V, tokens.shape[1], penalty, _stream()), "js2t_rep_penalty")
     return log_probs
 
 
@@ -905,8 +875,7 @@ def logp_set(log_probs: torch.Tensor, rows, cols, value: float):
     cols = torch.as_tensor(cols, dtype=torch.int64).to(dev).contiguous()
     if rows.numel() != cols.numel():
         raise Js2tError("logp_set: rows and cols differ in length")
-    check(lib().js2t_logp_set(_p(log_probs), _p(rows), _p(cols), C.c_int64(rows.numel()), C.c_int64(log_probs.shape[1]),
-                              C.c_float(value), _stream()), "js2t_logp_set")
+    check(lib().js2t_logp_set(_p(log_probs), _p(rows), _p(cols), rows.numel(), log_probs.shape[1], value, _stream()), "js2t_logp_set")
     return log_probs
 
 
@@ -926,8 +895,7 @@ def beam_step(logits2d: torch.Tensor, beam_log_probs: torch.Tensor, n_batch: int
     fb = (C.c_int32 * max(1, len(forbid_ids)))(*forbid_ids)
     blp = beam_log_probs.contiguous().float()
     fn = lib().js2t_beam_step_logp if normalized else lib().js2t_beam_step
-    check(fn(_p(logits2d), _p(blp), _p(scores), _p(ids), _p(lse), C.c_int64(n_batch), C.c_int32(beam),
-             C.c_int64(V), fb, C.c_int32(len(forbid_ids)), C.c_float(length_penalty), _stream()),
+    check(fn(_p(logits2d), _p(blp), _p(scores), _p(ids), _p(lse), n_batch, beam, V, fb, len(forbid_ids), length_penalty, _stream()),
           "js2t_beam_step")
     return scores, ids, lse
 
@@ -946,8 +914,8 @@ def beam_pick(logits2d: torch.Tensor, n_pick: int, forbid_ids, row_scores: Optio
     ids = torch.empty((rows, n_pick), dtype=torch.int64, device=dev)
     lse = torch.empty((rows, ), dtype=torch.float32, device=dev)
     fb = (C.c_int32 * max(1, len(forbid_ids)))(*forbid_ids)
-    check(lib().js2t_beam_pick(_p(logits2d), _p(row_scores.contiguous().float()), _p(scores), _p(ids), _p(lse), C.c_int64(rows), C.c_int32(n_pick),
-                               C.c_int64(V), fb, C.c_int32(len(forbid_ids)), _stream()), "js2t_beam_pick")
+    check(lib().js2t_beam_pick(_p(logits2d), _p(row_scores.contiguous().float()), _p(scores), _p(ids), _p(lse), rows, n_pick, V, fb,
+                               len(forbid_ids), _stream()), "js2t_beam_pick")
     return scores, ids, lse
 
 
@@ -979,10 +947,9 @@ def ctc_prefix_step(ctc_log_probs, in_len, r_prev, last_tok, cand, cand_lp, psi_
     local = torch.empty((rows, Cn), dtype=torch.float32, device=dev)
     psi = torch.empty((rows, Cn), dtype=torch.float32, device=dev)
     r_new = torch.empty((rows, Cn, T, 2), dtype=torch.float32, device=dev)
-    check(lib().js2t_ctc_prefix_step(_p(ctc_log_probs), _p(in_len.contiguous()), _p(r_prev), _p(last_tok.contiguous()), _p(cand.contiguous()),
-                                     _p(cand_lp.contiguous().float()), _p(psi_prev.contiguous().float()), _p(local), _p(psi), _p(r_new),
-                                     C.c_int64(rows), C.c_int32(beam), C.c_int32(Cn), C.c_int32(T), C.c_int64(V), C.c_int32(n_out),
-                                     C.c_int32(blank), C.c_int32(eos), C.c_float(weight), _stream()), "js2t_ctc_prefix_step")
+    check(lib().js2t_ctc_prefix_step(_p(ctc_log_probs), _p(in_len.contiguous()), _p(r_prev), _p(last_tok.contiguous()),
+                                     _p(cand.contiguous()), _p(cand_lp.contiguous().float()), _p(psi_prev.contiguous().float()), _p(local),
+                                     _p(psi), _p(r_new), rows, beam, Cn, T, V, n_out, blank, eos, weight, _stream()), "js2t_ctc_prefix_step")
     return local, psi, r_new
 
 
@@ -1057,8 +1024,7 @@ def pack_rows(x2d, pk: PackedRows):
     if x2d.dim() != 2 or x2d.shape[0] != pk.B * pk.T or not x2d.is_contiguous() or (x2d.shape[1] * x2d.element_size()) % 16:
         raise Js2tError(f"pack_rows: contiguous [{pk.B * pk.T}, C] rows of a multiple of 16 bytes, got {tuple(x2d.shape)}")
     out = torch.empty((pk.rows, x2d.shape[1]), dtype=x2d.dtype, device=x2d.device)
-    check(lib().js2t_pack_rows(C.c_void_p(x2d.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(pk.seg.data_ptr()), pk.B, pk.T,
-                               C.c_int64(pk.rows), C.c_int64(x2d.shape[1] * x2d.element_size()), 1, _stream()), "js2t_pack_rows")
+    check(lib().js2t_pack_rows(_p(x2d), _p(out), _p(pk.seg), pk.B, pk.T, pk.rows, x2d.shape[1] * x2d.element_size(), 1, _stream()), "js2t_pack_rows")
     return out
 
 
@@ -1068,8 +1034,7 @@ def unpack_rows(xp, pk: PackedRows):
     if xp.dim() != 2 or xp.shape[0] != pk.rows or not xp.is_contiguous() or (xp.shape[1] * xp.element_size()) % 16:
         raise Js2tError(f"unpack_rows: contiguous [{pk.rows}, C] rows of a multiple of 16 bytes, got {tuple(xp.shape)}")
     out = torch.empty((pk.B * pk.T, xp.shape[1]), dtype=xp.dtype, device=xp.device)
-    check(lib().js2t_pack_rows(C.c_void_p(xp.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(pk.seg.data_ptr()), pk.B, pk.T,
-                               C.c_int64(pk.rows), C.c_int64(xp.shape[1] * xp.element_size()), 0, _stream()), "js2t_pack_rows")
+    check(lib().js2t_pack_rows(_p(xp), _p(out), _p(pk.seg), pk.B, pk.T, pk.rows, xp.shape[1] * xp.element_size(), 0, _stream()), "js2t_pack_rows")
     return out
 
 
@@ -1078,8 +1043,7 @@ def zero_tail_rows(buf, pk: PackedRows):
     _dev(buf, pk.seg)
     if buf.dim() != 2 or buf.shape[0] != pk.rows or not buf.is_contiguous() or (buf.shape[1] * buf.element_size()) % 16:
         raise Js2tError(f"zero_tail_rows: contiguous [{pk.rows}, C] rows of a multiple of 16 bytes, got {tuple(buf.shape)}")
-    check(lib().js2t_pack_rows(C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr()), C.c_void_p(pk.seg.data_ptr()), pk.B, pk.T,
-                               C.c_int64(pk.rows), C.c_int64(buf.shape[1] * buf.element_size()), 2, _stream()), "js2t_pack_rows")
+    check(lib().js2t_pack_rows(_p(buf), _p(buf), _p(pk.seg), pk.B, pk.T, pk.rows, buf.shape[1] * buf.element_size(), 2, _stream()), "js2t_pack_rows")
 
 
 def _seg_check(pk, q_t, B, Tq, Tk, k_t=None):

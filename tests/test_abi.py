@@ -44,7 +44,7 @@ def test_no_cpu_fallback():
 def test_comm_entry_points_reject_bad_arguments():
     """js2t_comm_* (the RCCL communicator behind the boundary): argument checks only - no GPU, no RCCL call."""
     from joeys2t_amd import comm
-    L = comm._bind(_lib.lib())
+    L = _lib.lib()
     assert L.js2t_comm_unique_id_bytes() == 128
     assert L.js2t_comm_unique_id(None, 128) != 0 and b"128" in L.js2t_last_error()
     h = ctypes.c_void_p()
@@ -151,3 +151,98 @@ def test_context_settings_are_per_caller_not_per_process():
             lib().js2t_gemm_p192_ring(-1)
         assert _lib.effective("gemm_p192_ring") == 2  # ... and gives way again
     assert _lib.effective("deterministic") == 0 and _lib.effective("gemm_p192_ring") == -1
+
+
+# ---- the binding is derived from the header: signatures, struct layout, 64-bit values, unknown types -------------------------------
+_I, _I32, _I64, _F, _P = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+_KNOWN_SIGNATURES = {  # written out from include/joeys2t_hip.h by hand: (restype, argtypes)
+    "js2t_axpby": (_I, [_P, _F, _P, _F, _P, _I64, _I, _P]),
+    "js2t_attn_decode": (_I, [_P, _I64, _P, _P, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _I32, _I, _P]),
+    "js2t_ctc_align": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "js2t_gemm_grouped": (_I, [_P, _I32, _P, _P, _P, _P, _P]),
+    "js2t_comm_init": (_I, [_P, _P, _I64, _I32, _I32, _I32]),
+    "js2t_comm_stream": (_P, [_P]),
+    "js2t_last_error": (ctypes.c_char_p, []),
+    "js2t_sumsq_partials": (_I64, [_I64]),
+    "js2t_adamw_items_geometry": (None, [_P, _P, _P]),
+    "js2t_ctx_bind": (_P, [_P]),
+}
+
+
+def _prototypes():
+    """{name: (is_void, parameter count)} read off the header text without the package's parser"""
+    import re
+    text = re.sub(r"/\*.*?\*/", "", _lib.HEADER_PATH.read_text(), flags=re.S)
+    found = {}
+    for ret, name, params in re.findall(r"(\w[\w\s*]*?)\b(js2t_\w+)\s*\(([^)]*)\)\s*;", text):
+        found[name] = (ret.split() == ["void"], 0 if params.strip() == "void" else params.count(",") + 1)
+    return found
+
+
+def test_every_declared_function_is_bound_with_the_headers_signature():
+    handle, protos = _lib.lib(), _prototypes()
+    names = _lib.declared_symbols()
+    assert sorted(protos) == names
+    for name in names:
+        fn, (is_void, n_params) = getattr(handle, name), protos[name]
+        assert fn.argtypes is not None and len(fn.argtypes) == n_params, name
+        assert (fn.restype is None) == is_void, name
+    for name, (restype, argtypes) in _KNOWN_SIGNATURES.items():
+        fn = getattr(handle, name)
+        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
+
+
+def _host_cc():
+    import os
+    import shutil
+    for cand in ("cc", "gcc", "clang", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")):
+        if shutil.which(cand):
+            return shutil.which(cand)
+    return None
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """sizeof / offsetof of every field of both structs as the host C compiler lays them out == the ctypes classes derived from the
+    header (a field of the wrong width passes the name-order tests above and shifts everything behind it)"""
+    import subprocess
+    cc = _host_cc()
+    if cc is None:
+        pytest.skip("no host C compiler")
+    structs = {"js2t_gemm_desc": _lib.GemmDesc, "js2t_attn_desc": _lib.AttnDesc}
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "joeys2t_hip.h"', "int main(void) {"]
+    for cname, cls in structs.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        for field, _ in cls._fields_:
+            lines.append(f'  printf("{cname}.{field} %zu %zu\\n", offsetof({cname}, {field}), sizeof((({cname}*)0)->{field}));')
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", str(_lib.HEADER_PATH.parent), str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    want = []
+    for cname, cls in structs.items():
+        want.append(f"{cname} {ctypes.sizeof(cls)}")
+        want += [f"{cname}.{field} {getattr(cls, field).offset} {getattr(cls, field).size}" for field, _ in cls._fields_]
+    assert len(_lib.GemmDesc._fields_) == 59 and len(_lib.AttnDesc._fields_) == 38
+    assert [g for g in got if g] == want
+
+
+def test_64_bit_arguments_and_returns_survive():
+    """host-only entry points: a value above 2^32 arrives and comes back whole; a float for an int64_t never leaves Python"""
+    L = _lib.lib()
+    assert L.js2t_colsum_partial_rows(2**40) == 2**34   # CS_ROWS_PER_BLOCK = 64 (elementwise.hip)
+    assert L.js2t_sumsq_partials(2**40) == 2**26        # SQ_PER_BLOCK = 16384 (optim.hip)
+    assert L.js2t_ctc_align_workspace_bytes(-1, 1, 1) == 0
+    with pytest.raises(ctypes.ArgumentError):
+        L.js2t_axpby(None, 1.5, None, 0.0, None, 2.5, 0, None)
+
+
+def test_unknown_type_in_the_header_fails_loudly():
+    structs, functions = _lib.parse_header("typedef struct s { int32_t a, *b; const float* c; } s_t;\nint64_t js2t_x(const void* const* p, double v);")
+    assert structs == {"s_t": [("a", ctypes.c_int32), ("b", _P), ("c", _P)]} and functions == {"js2t_x": (_I64, [_P, ctypes.c_double])}
+    with pytest.raises(_lib.Js2tError, match="long double"):
+        _lib.parse_header("int js2t_x(long double v);")
+    with pytest.raises(_lib.Js2tError, match="size_t"):
+        _lib.parse_header("typedef struct s { size_t n; } s_t;")
+    with pytest.raises(_lib.Js2tError, match="js2t_y"):  # a declaration the prototype pattern cannot read is an error, not a default
+        _lib.parse_header("int js2t_y(int (*cb)(int));")
