@@ -445,6 +445,39 @@ int js2t_ctc_align(const void* logits, int dt, const float* lse, const int64_t* 
                    float* score, void* workspace, int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t blank,
                    const int32_t* row_offsets, js2t_stream stream);
 
+/* EXTENSION (the reference has no encoder-only n-best decoder): CTC prefix beam search - the beam search over the CTC output alone
+ * that sums the probability of ALL alignments of a labelling (js2t_ctc_collapse reads the best path only).  One launch, one block
+ * per utterance; natural logarithms, f32.  logits / lse / in_len / blank / row_offsets and the clamp T_b = clamp(in_len[b], 0, T) as
+ * in js2t_ctc_align; lp_t(v) = logits[row(b,t), v] - lse[row(b,t)].
+ * Candidates: cand_id i64 / cand_lp f32 [rows, n_cand], addressed by the same rows as the logits (js2t_beam_pick with the blank
+ * forbidden makes them): cand_lp = lp_t of cand_id, the ids of a row distinct.  An entry is ignored if its id is the blank or
+ * outside 0 .. V-1, or its cand_lp is -inf (or NaN).  The blank is always allowed, lp_t(blank) read from logits and lse.  The
+ * search is EXACT prefix beam search over the distribution truncated to the blank and the frame's candidates.
+ * Recursion: the beam starts as {(): pb = 0, pnb = -inf} (log-mass of the alignments that end in blank / in non-blank);
+ * lae = logaddexp with lae(-inf, x) = x.  Per frame, for every prefix y of the beam, tot = lae(pb, pnb), e = its last label:
+ *   next[y].pb (+)= tot + lp_t(blank);   for every candidate (c, lp):
+ *   c == e: next[y].pnb (+)= pnb + lp and next[y+c].pnb (+)= pb + lp (skipped when pb = -inf);   else: next[y+c].pnb (+)= tot + lp
+ * `next` is keyed by the TOKEN SEQUENCE: contributions that reach one sequence from anywhere add up.  The new beam is the `beam`
+ * entries of `next` with the largest lae(pb, pnb); after frame T_b - 1 the n_best best prefixes are returned, best first.
+ * Identity of a sequence: its length and a 64-bit hash carried per prefix, h(()) = 0x9E3779B97F4A7C15, h(y+c) = fmix(h(y) ^ (c + 1)),
+ * fmix(z) = the finaliser of splitmix64 (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).
+ * fmix is a bijection, so the children of one prefix never collide; two different sequences of one length collide with
+ * probability 2^-64 per comparison if fmix is taken as random, and a frame compares at most beam * (beam + beam * n_cand) pairs:
+ * < 2^-40 per utterance of 1000 frames at the limits below.
+ * Ties (deterministic; no atomics, the same bits on every run and under graph replay): among equal scores the prefixes that were in
+ * the beam come first, by their rank there, then the extensions by (rank of the parent, candidate slot).
+ * Limits: 1 <= beam <= 32, 1 <= n_cand <= 8, 1 <= n_best <= beam, beam * T < 2^31.
+ * out_ids i64 [B, n_best, T] pad-filled, out_len i32 [B, n_best], out_score f32 [B, n_best] = lae(pb, pnb).  Slots beyond the number
+ * of distinct prefixes that exist (short utterances): score -inf, length 0, all pad.  T_b = 0: the empty hypothesis with score 0 in
+ * slot 0.  Utterances do not affect each other; nothing behind an utterance's length is read.
+ * workspace: js2t_ctc_beam_workspace_bytes bytes (the trie: a (parent, token) node per survivor and frame; contents on entry do
+ * not matter).  No allocation, no synchronisation: capturable. */
+int64_t js2t_ctc_beam_workspace_bytes(int64_t B, int64_t T, int32_t beam);
+int js2t_ctc_beam_search(const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+                         const int64_t* in_len, int64_t* out_ids, int32_t* out_len, float* out_score, void* workspace,
+                         int64_t B, int64_t T, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best,
+                         int64_t blank, int64_t pad, const int32_t* row_offsets, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

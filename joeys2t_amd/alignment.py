@@ -38,16 +38,16 @@ def frame_seconds(model, frame_shift_ms: float = 10.0) -> float:
     return (2 ** (sub.n_layers if sub is not None else 0)) * frame_shift_ms / 1000.0
 
 
-def _ctc_frames(model, batch):
-    """(ctc logits [B, T', V], lse [B * T'], input lengths i64[B]) the way search.ctc_greedy obtains them"""
+def _ctc_frames(model, batch, who: str = "forced_align", want_lse: bool = True):
+    """(ctc logits [B, T', V], lse [B * T'] or None, input lengths i64[B]) the way search.ctc_greedy obtains them"""
     from joeys2t_amd import ops
     layer = getattr(model.decoder, "ctc_output_layer", None)
     if layer is None:
-        raise ValueError("forced_align: the model has no CTC output layer (loss: crossentropy-ctc)")
+        raise ValueError(f"{who}: the model has no CTC output layer (loss: crossentropy-ctc)")
     encoder_output, _, src_mask, _ = model(return_type="encode", **vars(batch))
     ctc_out = model.decoder.project(layer, encoder_output, model.runtime.compute_dtype).contiguous()  # [B, T', V]
     B, T, V = ctc_out.shape
-    lse, _ = ops.row_lse(ctc_out.view(B * T, V))
+    lse = ops.row_lse(ctc_out.view(B * T, V))[0] if want_lse else None
     in_len = src_mask.squeeze(1).sum(dim=1).to(torch.int64).contiguous()
     return ctc_out, lse, in_len
 

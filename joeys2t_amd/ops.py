@@ -796,6 +796,53 @@ def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "Packed
     return path, tok_start, tok_end, frame_logp, score
 
 
+def ctc_beam_workspace_bytes(B: int, T: int, beam: int) -> int:
+    return lib().js2t_ctc_beam_workspace_bytes(B, T, beam)
+
+
+def ctc_beam_candidates(logits2d: torch.Tensor, n_cand: int, blank: int):
+    """The candidate tables of ctc_beam_search: for every row of f32 logits [rows, V] the n_cand (<= 8, <= V - 1) most probable
+    LABELS (js2t_beam_pick with the blank forbidden, so every slot is a label).  Returns (cand_id i64 [rows, n_cand],
+    cand_lp f32 [rows, n_cand], lse f32 [rows])."""
+    if n_cand > logits2d.shape[1] - 1:
+        raise Js2tError(f"ctc_beam_candidates: {n_cand} candidates for {logits2d.shape[1] - 1} labels")
+    cand_lp, cand_id, lse = beam_pick(logits2d, n_cand, [int(blank)])
+    return cand_id, cand_lp, lse
+
+
+def ctc_beam_search(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: int, blank: int, pad: int, pack: "PackedRows" = None,
+                    workspace=None):
+    """CTC prefix beam search (js2t_ctc_beam_search): logits / lse / in_len / pack as for ctc_alpha; cand_id i64 / cand_lp f32
+    [rows, n_cand] the candidate labels of every logits row and their log-probabilities (ctc_beam_candidates).  Returns
+    (ids i64 [B, n_best, T] pad-filled, lengths i32 [B, n_best], scores f32 [B, n_best], best first; -inf / 0 / pad in the slots an
+    utterance has no prefix for).  workspace: a device buffer of >= ctc_beam_workspace_bytes(B, T, beam) bytes to use instead of a
+    fresh one (contents are ignored)."""
+    _dev(logits3d, lse, cand_id, cand_lp, in_len, workspace)
+    B, T, V, roff = _ctc_geometry(logits3d, pack)
+    rows = logits3d.numel() // V
+    if cand_id.dim() != 2 or cand_id.shape[0] != rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
+            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
+        raise Js2tError(f"ctc_beam_search: contiguous candidate tables i64 / f32 [{rows}, n_cand] expected, got "
+                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
+    if lse.numel() != rows or lse.dtype != torch.float32 or not logits3d.is_contiguous() or not lse.is_contiguous():
+        raise Js2tError(f"ctc_beam_search: contiguous logits and f32 lse [{rows}] expected")
+    dev = logits3d.device
+    in_len = in_len.to(torch.int64).contiguous()
+    need = ctc_beam_workspace_bytes(B, T, beam)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"ctc_beam_search: a contiguous workspace of {need} bytes expected")
+    nb = max(int(n_best), 0)
+    ids = torch.empty((B, nb, T), dtype=torch.int64, device=dev)
+    n = torch.empty((B, nb), dtype=torch.int32, device=dev)
+    score = torch.empty((B, nb), dtype=torch.float32, device=dev)
+    check(lib().js2t_ctc_beam_search(_p(logits3d), dt_code(logits3d), _p(lse), _p(cand_id), _p(cand_lp), _p(in_len), _p(ids), _p(n),
+                                     _p(score), _p(workspace), B, T, V, beam, cand_id.shape[1], n_best, blank, pad, roff, _stream()),
+          "js2t_ctc_beam_search")
+    return ids, n, score
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the

@@ -20,20 +20,27 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import search
+from joeys2t_amd.search import ctc_beam_search, search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
             max_output_length: int = -1, min_output_length: int = 1, generate_unk: bool = True,
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
-            return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1):
+            return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
+            decoder: str = "attention", ctc_candidates: int = 8):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
     {"totals": {loss, n_correct, ntokens, nseqs}, "normalizer", "valid_scores": {loss, acc, ppl}}.
     return_prob="ref": ids are the reference tokens and scores their log-probabilities (one array per sentence), no search.
     Under a process group every rank passes ITS batches; totals are sums over ranks, and rank 0's outputs hold all ranks'
-    sentences in dataset order (`batch.indices`), as in the reference (prediction.py:222-231, 250-257)."""
+    sentences in dataset order (`batch.indices`), as in the reference (prediction.py:222-231, 250-257).
+    decoder="ctc" (EXTENSION): hypotheses come from the CTC output layer alone - `search.ctc_beam_search` with a beam of `beam_size`
+    (any value >= 1) over the `ctc_candidates` best labels of every frame; scores (with return_prob="hyp") are the log-probabilities
+    of the labellings; the options of the attention decoder (beam_alpha, output lengths, penalties, attention) do not apply."""
+    if decoder not in ("attention", "ctc"):
+        raise ValueError(f"predict: decoder '{decoder}' is neither 'attention' nor 'ctc'")
+    ctc = decoder == "ctc"
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}
     totals: Dict[str, float] = {"loss": 0.0, "n_correct": 0, "ntokens": 0, "nseqs": 0}
@@ -60,7 +67,10 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             totals["loss"] += float(batch_loss.sum().item())
             totals["n_correct"] += int(n_correct.sum().item())
             totals["ntokens"] += int(batch_ntokens.sum().item())
-        if return_prob != "ref":
+        if return_prob != "ref" and ctc:
+            ids, scores, _ = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates)
+            scores = scores if return_prob == "hyp" else None
+        elif return_prob != "ref":
             ids, scores, att = search(model=model, batch=batch, beam_size=beam_size, beam_alpha=beam_alpha, n_best=n_best,
                                       max_output_length=max_output_length, min_output_length=min_output_length,
                                       generate_unk=generate_unk, return_prob=return_prob,
@@ -71,7 +81,7 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             # the reference's does, search.py:333-335); beam search returns this rank's rows, so they are merged here (extension: the
             # reference's beam search does not merge, and its assert below then fails for world_size > 1).  The order of merged
             # outputs is unknown: they are put back by `indices` after the loop (prediction.py:222-231).
-            if return_prob != "ref" and beam_size >= 2:
+            if return_prob != "ref" and (beam_size >= 2 or ctc):
                 ids = ddp_merge(torch.as_tensor(np.asarray(ids), device=device), model.pad_index).cpu().numpy()
                 if scores is not None:
                     scores = ddp_merge(torch.as_tensor(np.asarray(scores), device=device), 0.0).cpu().numpy()

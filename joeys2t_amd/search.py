@@ -486,3 +486,25 @@ def ctc_greedy(model, batch):
         ids, n = ops.ctc_collapse(best.view(B, T), in_len, model.bos_index, model.pad_index)
     return ids.cpu().numpy(), n.cpu().numpy()
 
+
+
+def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8):
+    """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
+    `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
+    `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
+    Returns NumPy in the row layout of `beam_search`: ids i64 [B * n_best, L] pad-filled (L = the longest hypothesis, at least 1),
+    scores f32 [B * n_best, 1] (log-probability of the labelling under the truncated distribution; -inf with an all-pad row where
+    an utterance has fewer than n_best prefixes) and lengths i64 [B * n_best]."""
+    from joeys2t_amd.alignment import _ctc_frames
+    if not 1 <= n_best <= beam_size:
+        raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
+    with torch.no_grad():
+        ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
+        B, T, V = ctc_out.shape
+        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
+        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+        ids, n, score = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, int(beam_size), int(n_best), model.bos_index,
+                                            model.pad_index)
+    n = n.cpu().numpy().astype(np.int64).reshape(B * n_best)
+    L = max(int(n.max()) if n.size else 0, 1)
+    return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
