@@ -298,13 +298,7 @@ int al_launch(bool wave, size_t lds, hipStream_t s, int64_t B, const void* logit
               float* score, uint32_t* ws, int64_t ws_words, int bp_words, int64_t T_, int64_t V, int64_t Lmax, int64_t blank,
               const int32_t* row_offsets) {
   auto kern = wave ? ctc_align_wave_kernel<T> : ctc_align_block_kernel<T>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-  }
+  if (lds > 48 * 1024 && js2t_lds_optin((const void*)kern, (int)lds) != JS2T_OK) return JS2T_ERR_LAUNCH;
   hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(AL_THREADS), lds, s, (const T*)logits, lse, targets, in_len, tgt_len, path, tok_start,
                      tok_end, frame_logp, score, ws, ws_words, bp_words, T_, V, Lmax, blank, row_offsets);
   JS2T_LAUNCH_CHECK();

@@ -942,16 +942,6 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_kernel(AttnArgs a, int n_dkv
   else if ((int)blockIdx.x >= n_dkv_pad) flash_dq_body<DH, REL, DROP>(a, (int)blockIdx.x - n_dkv_pad, (int)gridDim.x - n_dkv_pad);
 }
 
-template <typename K>
-int set_lds(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return JS2T_ERR_LAUNCH;
-  }
-  return JS2T_OK;
-}
-
 int check_common(const js2t_attn_desc* d) {
   JS2T_CHECK(d != nullptr, "flash_attn: null descriptor");
   JS2T_CHECK(d->head_dim == 128 || d->head_dim == 64, "flash_attn: head size %d not supported (128 or 64; use the unfused path)",
@@ -996,14 +986,8 @@ int g_attn_fwd_sb = -1;  // -1: by shape, 0 / 1: forced (js2t_debug_attn_fwd_sb;
 bool g_attn_bwd_merge = true;  // js2t_debug_attn_bwd_merge(0): the two passes as two launches also with delta_partial (A/B)
 template <int DH, bool REL, bool DROP>
 int launch_fwd(const js2t_attn_desc* d, hipStream_t s) {
-  static bool once = false;
-  if (!once) {
-    int rc = set_lds(flash_fwd_kernel<DH, REL, false, DROP>, 4 * IMG_BYTES);
-    if (rc) return rc;
-    rc = set_lds(flash_fwd_kernel<DH, REL, true, DROP>, 2 * IMG_BYTES + KMASK_MAX / 8);
-    if (rc) return rc;
-    once = true;
-  }
+  JS2T_LDS_ONCE((flash_fwd_kernel<DH, REL, false, DROP>), 4 * IMG_BYTES);
+  JS2T_LDS_ONCE((flash_fwd_kernel<DH, REL, true, DROP>), 2 * IMG_BYTES + KMASK_MAX / 8);
   AttnArgs a = to_args(d);
   const int nblk = cdiv(d->Tq, 64) * d->B * d->H;
   constexpr int KT = Geo<DH>::KT;
@@ -1018,16 +1002,9 @@ int launch_fwd(const js2t_attn_desc* d, hipStream_t s) {
 
 template <int DH, bool REL, bool DROP>
 int launch_bwd(const js2t_attn_desc* d, hipStream_t s) {
-  static bool once = false;
-  if (!once) {
-    int rc = set_lds(flash_dq_kernel<DH, REL, DROP>, 4 * IMG_BYTES);
-    if (rc) return rc;
-    rc = set_lds(flash_dkv_kernel<DH, REL, DROP>, 4 * IMG_BYTES);
-    if (rc) return rc;
-    rc = set_lds(flash_bwd_kernel<DH, REL, DROP>, 4 * IMG_BYTES);
-    if (rc) return rc;
-    once = true;
-  }
+  JS2T_LDS_ONCE((flash_dq_kernel<DH, REL, DROP>), 4 * IMG_BYTES);
+  JS2T_LDS_ONCE((flash_dkv_kernel<DH, REL, DROP>), 4 * IMG_BYTES);
+  JS2T_LDS_ONCE((flash_bwd_kernel<DH, REL, DROP>), 4 * IMG_BYTES);
   AttnArgs a = to_args(d);
   const int n_dq = cdiv(d->Tq, 64) * d->B * d->H, n_dkv = cdiv(d->Tk, 64) * d->B * d->H;
   // deterministic mode (js2t_set_deterministic): the bias gradient's histogram as integer sums in a library scratch, converted

@@ -29,6 +29,22 @@ void js2t_set_error(const char* fmt, ...);
     }                                                                    \
   } while (0)
 
+// Launch plumbing (core.cpp).  js2t_lds_optin lets `kernel` take `bytes` of dynamic LDS (more than the 48 KB default): JS2T_OK, or
+// JS2T_ERR_LAUNCH with HIP's message in the error string.  Launchers whose size depends on the shape call it per launch; a kernel
+// with one fixed size opts in through JS2T_LDS_ONCE, once per process: the static caches HIP's code (initialised once and
+// thread-safe, C++11), and a cached failure is reported again on every call because the error string is per thread.
+// js2t_cu_count8: the CUs of the current device rounded down to a multiple of 8 (a persistent block's tiles then stay on one XCD's
+// slice of the tile order), the raw count below 8; <= 0 with the error string set when the query fails.
+hipError_t js2t_lds_optin_raw(const void* kernel, int bytes);
+int js2t_lds_optin_error(hipError_t e);
+int js2t_lds_optin(const void* kernel, int bytes);
+int js2t_cu_count8();
+#define JS2T_LDS_ONCE(kernel, bytes)                                                      \
+  do {                                                                                    \
+    static const hipError_t e__ = js2t_lds_optin_raw((const void*)(kernel), (bytes));     \
+    if (e__ != hipSuccess) return js2t_lds_optin_error(e__);                              \
+  } while (0)
+
 // Per-caller settings (core.cpp, js2t_ctx_* of the header): the value of `key` for the launch being made - the process-wide test
 // override if one is set, else the context bound to the calling thread (js2t_ctx_bind), else the built-in default.
 int js2t_ctx_value(int key);

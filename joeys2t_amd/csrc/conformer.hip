@@ -81,13 +81,9 @@ bool dwconv_outer_lds_launch(const void* x, const float* w, const float* bias, v
                              hipStream_t s) {
   if (dt != JS2T_BF16 || (C & 127) || L > 64 || L < 1 || ((((uintptr_t)x) | ((uintptr_t)y)) & 3) || (N + 3) / 4 > 65535) return false;
   const size_t lds = (size_t)L * 1024 + (size_t)K * 64 * sizeof(float2);
-  static bool once = false;
-  if (!once) {
-    if (hipFuncSetAttribute((const void*)dwconv_outer_lds_kernel<FLIP>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 + 63 * 512) !=
-        hipSuccess)
-      return false;
-    once = true;
-  }
+  // (JS2T_LDS_ONCE written out: a failure is no error here, the caller falls back to its plain kernel)
+  static const hipError_t lds_e = js2t_lds_optin_raw((const void*)dwconv_outer_lds_kernel<FLIP>, 64 * 1024 + 63 * 512);
+  if (lds_e != hipSuccess) return false;
   hipLaunchKernelGGL(dwconv_outer_lds_kernel<FLIP>, dim3((unsigned)(C / 128), (unsigned)((N + 3) / 4)), dim3(256), lds, s,
                      (const uint16_t*)x, w, bias, (uint16_t*)y, (int)L, N, C, K);
   return true;

@@ -1,12 +1,8 @@
-// Error channel and identity of libjoeys2t_hip.so.
+// Error channel, launch plumbing, per-caller settings and identity of libjoeys2t_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "../../include/joeys2t_hip.h"
-
-void js2t_set_error(const char* fmt, ...);
-int js2t_ctx_value(int key);
-void js2t_ctx_override(int key, int value);
+#include "common.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -15,6 +11,31 @@ void js2t_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// Launch plumbing shared by every launcher (declared in common.hpp).
+hipError_t js2t_lds_optin_raw(const void* kernel, int bytes) {
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+int js2t_lds_optin_error(hipError_t e) {
+  js2t_set_error("dynamic LDS opt-in: %s", hipGetErrorString(e));
+  return JS2T_ERR_LAUNCH;
+}
+int js2t_lds_optin(const void* kernel, int bytes) {
+  const hipError_t e = js2t_lds_optin_raw(kernel, bytes);
+  return e == hipSuccess ? JS2T_OK : js2t_lds_optin_error(e);
+}
+// Fetched once per process: the library assumes one device per process (data-parallel training runs one process per GPU).
+int js2t_cu_count8() {
+  static const int cu = [] {  // the count, or minus HIP's error code
+    int dev = 0, n = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return e == hipSuccess ? n : -(int)e;
+  }();
+  if (cu > 0) return (cu & ~7) ? (cu & ~7) : cu;
+  js2t_set_error("CU count query: %s", hipGetErrorString((hipError_t)-cu));
+  return 0;
 }
 
 extern "C" const char* js2t_last_error(void) { return g_err; }

@@ -1307,21 +1307,10 @@ inline bool w256_eligible(const js2t_gemm_desc& d) {
   if ((d.N & 7) || d.M < 256 || d.N < 256) return false;
   if (!g_force_w256 && ((int64_t)cdiv(d.M, 256) * cdiv(d.N, 256) < 512 || d.K < 1024)) return false;
   if (d.preact || d.beta != 0.f || !(d.act == JS2T_ACT_NONE || d.act == JS2T_ACT_RELU) || (d.residual && d.gate)) return false;
-  if ((((uintptr_t)d.C) & 15) || (d.ldc & 7)) return false;
-  if (d.residual && ((d.ldr & 7) || (((uintptr_t)d.residual) & 15))) return false;
-  if (d.gate && ((d.ldg & 7) || (((uintptr_t)d.gate) & 15))) return false;
-  return true;
+  return epilogue_rows_aligned(d);
 }
 int launch_bf16_w256(const js2t_gemm_desc& d, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_w256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE(gemm_bf16_w256_kernel, W_LDS);
   const int tm = cdiv(d.M, 256), tn = cdiv(d.N, 256);
   hipLaunchKernelGGL(gemm_bf16_w256_kernel, dim3(tm * tn), dim3(512), W_LDS, s, d, tm, tn);
   JS2T_LAUNCH_CHECK();
@@ -2818,88 +2807,50 @@ inline bool p192_eligible(const js2t_gemm_desc& d) {
   if (d.trans_a || d.trans_b || d.conv || d.split_k > 1 || d.batch != 1 || d.dtype_c != JS2T_BF16) return false;
   if ((d.N & 7) || d.N < 128 || (d.K & 7) || d.K < 192 || d.M < 1) return false;
   if (d.preact || d.beta != 0.f || !(d.act == JS2T_ACT_NONE || d.act == JS2T_ACT_RELU) || (d.residual && d.gate)) return false;
-  if ((((uintptr_t)d.C) & 15) || (d.ldc & 7)) return false;
-  if (d.residual && ((d.ldr & 7) || (((uintptr_t)d.residual) & 15))) return false;
-  if (d.gate && ((d.ldg & 7) || (((uintptr_t)d.gate) & 15))) return false;
+  if (!epilogue_rows_aligned(d)) return false;
   if (g_p192_mode < 0 && (int64_t)cdiv(d.M, P_BM) * (d.N >> 7) < 200) return false;
   return true;
 }
-// variant: 3 / 2 / 4 forced, -1 (default) by shape (measured on MI355X, tools/p192_ring_ab.py):
-//  * at least one and a half tiles per CU -> two blocks per CU on two-slot rings (QKV x1.15, FFN1 x1.23, ReLU-gated input
-//    gradient x1.23, CTC projection x1.11 over the single block with a three-slot ring);
-//  * fewer (N = 512: one tile per CU) -> ONE block of eight multiplying + four requesting waves (gemm_bf16_p192s_kernel:
-//    FFN2 x1.15, dQKV x1.16, dFFN1 x1.16, output projection x1.15); two blocks per CU lose 3-10 % there.
+// Which form of the persistent kernel takes a product of `tiles` 192x128 tiles on n_cu CUs: the loader / consumer form (ONE block
+// of eight multiplying + four requesting waves per CU, gemm_bf16_p192s_kernel) or two / one block(s) per CU on a two- / three-slot
+// ring.  ring (JS2T_CTX_GEMM_P192_RING): 4 / 2 / 3 force a form, -1 (default) goes by shape, measured on MI355X.
+//  bf16 (tools/p192_ring_ab.py):
+//  * more than one tile per CU -> two blocks per CU on two-slot rings (QKV x1.15, FFN1 x1.23, ReLU-gated input gradient x1.23,
+//    CTC projection x1.11 over the single block with a three-slot ring);
+//  * at most one tile per CU, i.e. ONE round (N = 512) -> the loader / consumer form (FFN2 x1.15, dQKV x1.16, dFFN1 x1.16, output
+//    projection x1.15); two blocks per CU lose 3-10 % there.  Between one and one and a half tiles per CU that form would need a second
+//    round for the few tiles left over (12288 < M <= 18432 rows at N = 512: the memory K | V input gradient on the padded rows of a
+//    ragged batch, 284 tiles, took two tile times) - the two-block form has them all resident at once;
+//  * the row statistics and row dots (PE_STATS, PE_DOT) are written by the loader / consumer form only: its multiplying waves issue
+//    no LDS-DMA, so the fences of the hand-over to the finishing wave wait for nothing but the wave's own stores.
+//  e4m3 (tools/fp8_gemm_bench.py): with the block-scaled instruction (one v_mfma_scale_f32_16x16x128_f8f6f4 per accumulator and
+//  stage) the loader / consumer form wins on every shape, also where the bf16 products prefer two blocks per CU: FFN1 23.3 against
+//  25.3 us, QKV 19.5 / 20.9, FFN2 15.5 / 23.1.  Without it (-DJS2T_FP8_NO_SCALED) that form takes fewer than one and a half tiles per
+//  CU, the two-block form the rest, and the e4m3 second output (c8) lives in the ring forms only.
 #define g_p192_ring js2t_ctx_value(JS2T_CTX_GEMM_P192_RING)
-template <int EPI>
-int launch_bf16_p192_epi(const js2t_gemm_desc& d, hipStream_t s) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_p192_kernel<EPI, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_bf16_p192_kernel<EPI, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_bf16_p192s_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    int dev = 0, cu = 0;
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu <= 0) {
-      js2t_set_error("gemm p192 setup: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    n_cu = cu & ~7;  // a multiple of 8 keeps a block's tiles on one XCD's slice of the tile order
-    if (n_cu == 0) n_cu = cu;
-  }
-  const int tm = cdiv(d.M, P_BM), tn = cdiv(d.N, 128);
-  // the row statistics (rs_*) are written by the loader / consumer form only: its multiplying waves issue no LDS-DMA, so the
-  // fences of the hand-over to the finishing wave wait for nothing but the wave's own stores
-  // one block of twelve waves per CU while the tiles fit ONE round (<= one per CU); between one and one and a half tiles per CU that
-  // form needs a second round for the few tiles left over (12288 < M <= 18432 rows at N = 512: the memory K | V input gradient on
-  // the padded rows of a ragged batch, 284 tiles, took two tile times) - the two-block form has them all resident at once
-  if (g_p192_ring == 4 || (EPI >= 0 && (EPI & (PE_STATS | PE_DOT))) || (g_p192_ring < 0 && tm * tn <= n_cu)) {
-    const int grid = tm * tn < n_cu ? tm * tn : n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192s_kernel<EPI>), dim3(grid), dim3(768), PS_LDS, s, d, tm, tn);
-  } else if (g_p192_ring == 2 || (g_p192_ring < 0 && tm * tn > n_cu)) {
-    const int grid = tm * tn < 2 * n_cu ? tm * tn : 2 * n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192_kernel<EPI, 2>), dim3(grid), dim3(256), 2 * P_STAGE, s, d, tm, tn);
-  } else {
-    const int grid = tm * tn < n_cu ? tm * tn : n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192_kernel<EPI, 3>), dim3(grid), dim3(256), P_LDS, s, d, tm, tn);
-  }
-  JS2T_LAUNCH_CHECK();
-  return JS2T_OK;
+enum P192Form { P192_LOADER_CONSUMER, P192_RING2, P192_RING3 };
+inline P192Form p192_form(int tiles, int n_cu, int ring, bool stats_dot, bool fp8, bool c8, bool scaled) {
+  const bool few = fp8 ? 2 * tiles < 3 * n_cu : tiles <= n_cu;
+  const bool lc = fp8 ? (scaled && ring < 0) || ((scaled || !c8) && (ring == 4 || (ring < 0 && few)))
+                      : ring == 4 || stats_dot || (ring < 0 && few);
+  if (lc) return P192_LOADER_CONSUMER;
+  return (ring == 2 || (ring < 0 && !few)) ? P192_RING2 : P192_RING3;
 }
-// e4m3 operands: generic epilogue only (alpha carries the two per-tensor scales), ring depth by the same rule
-int launch_fp8_p192(const js2t_gemm_desc& d, hipStream_t s) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_p192_kernel<-1, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_bf16_p192_kernel<-1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P_STAGE);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_bf16_p192s_kernel<-1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    int dev = 0, cu = 0;
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu <= 0) {
-      js2t_set_error("gemm fp8 setup: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    n_cu = (cu & ~7) ? (cu & ~7) : cu;
-  }
-  const int tm = cdiv(d.M, P_BM), tn = cdiv(d.N, 128);
-  if ((P192S_SCALED && g_p192_ring < 0) || ((P192S_SCALED || !d.c8) && (g_p192_ring == 4 || (g_p192_ring < 0 && 2 * tm * tn < 3 * n_cu)))) {
-    // eight multiplying + four requesting waves.  With the block-scaled instruction (one v_mfma_scale_f32_16x16x128_f8f6f4 per
-    // accumulator and stage) this form wins on every shape, also above 1.5 tiles per CU where the bf16 products prefer two blocks
-    // per CU: FFN1 23.3 against 25.3 us, QKV 19.5 / 20.9, FFN2 15.5 / 23.1 (tools/fp8_gemm_bench.py); without it (-DJS2T_FP8_NO_SCALED)
-    // the bf16 rule applies and the e4m3 second output lives in the ring forms only
-    const int grid = tm * tn < n_cu ? tm * tn : n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192s_kernel<-1, true>), dim3(grid), dim3(768), PS_LDS, s, d, tm, tn);
-  } else if (g_p192_ring == 2 || (g_p192_ring < 0 && 2 * tm * tn >= 3 * n_cu)) {
-    const int grid = tm * tn < 2 * n_cu ? tm * tn : 2 * n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192_kernel<-1, 2, true>), dim3(grid), dim3(256), 2 * P_STAGE, s, d, tm, tn);
-  } else {
-    const int grid = tm * tn < n_cu ? tm * tn : n_cu;
-    hipLaunchKernelGGL((gemm_bf16_p192_kernel<-1, 3, true>), dim3(grid), dim3(256), P_LDS, s, d, tm, tn);
+// EPI: the epilogue terms of the instantiation (PE_*), -1 = decided at run time.  FP8: e4m3 operands, generic epilogue only (alpha
+// carries the two per-tensor scales).
+template <int EPI, bool FP8 = false>
+int launch_p192_epi(const js2t_gemm_desc& d, hipStream_t s) {
+  JS2T_LDS_ONCE((gemm_bf16_p192_kernel<EPI, 3, FP8>), P_LDS);
+  JS2T_LDS_ONCE((gemm_bf16_p192_kernel<EPI, 2, FP8>), 2 * P_STAGE);
+  JS2T_LDS_ONCE((gemm_bf16_p192s_kernel<EPI, FP8>), PS_LDS);
+  const int n_cu = js2t_cu_count8();
+  if (n_cu <= 0) return JS2T_ERR_LAUNCH;
+  const int tm = cdiv(d.M, P_BM), tn = cdiv(d.N, 128), tiles = tm * tn;
+  const int one = tiles < n_cu ? tiles : n_cu, two = tiles < 2 * n_cu ? tiles : 2 * n_cu;  // grid: one / two block(s) per CU
+  switch (p192_form(tiles, n_cu, g_p192_ring, EPI >= 0 && (EPI & (PE_STATS | PE_DOT)), FP8, d.c8 != nullptr, P192S_SCALED)) {
+    case P192_LOADER_CONSUMER: hipLaunchKernelGGL((gemm_bf16_p192s_kernel<EPI, FP8>), dim3(one), dim3(768), PS_LDS, s, d, tm, tn); break;
+    case P192_RING2: hipLaunchKernelGGL((gemm_bf16_p192_kernel<EPI, 2, FP8>), dim3(two), dim3(256), 2 * P_STAGE, s, d, tm, tn); break;
+    case P192_RING3: hipLaunchKernelGGL((gemm_bf16_p192_kernel<EPI, 3, FP8>), dim3(one), dim3(256), P_LDS, s, d, tm, tn); break;
   }
   JS2T_LAUNCH_CHECK();
   return JS2T_OK;
@@ -2914,17 +2865,17 @@ int launch_bf16_p192(const js2t_gemm_desc& d, hipStream_t s) {
     const int rc = launch_bf16_pan96(d, mask, s);
     if (rc >= 0) return rc;
     switch (mask) {
-      case PE_BIAS | PE_LNF: return launch_bf16_p192_epi<PE_BIAS | PE_LNF>(d, s);      // q/k/v projections on the raw residual stream
-      case PE_BIAS | PE_RELU | PE_DROP | PE_LNF: return launch_bf16_p192_epi<PE_BIAS | PE_RELU | PE_DROP | PE_LNF>(d, s);  // FFN layer 1, same
-      case PE_BIAS | PE_DROP | PE_RES | PE_STATS: return launch_bf16_p192_epi<PE_BIAS | PE_DROP | PE_RES | PE_STATS>(d, s);  // + next LN's row sums
-      case PE_BIAS | PE_RELU | PE_LNF: return launch_bf16_p192_epi<PE_BIAS | PE_RELU | PE_LNF>(d, s);  // evaluation mode (no dropout)
-      case PE_BIAS | PE_RES | PE_STATS: return launch_bf16_p192_epi<PE_BIAS | PE_RES | PE_STATS>(d, s);
-      case 0: return launch_bf16_p192_epi<0>(d, s);                                    // input gradients
-      case PE_BIAS: return launch_bf16_p192_epi<PE_BIAS>(d, s);                        // q/k/v projections
-      case PE_BIAS | PE_RELU | PE_DROP: return launch_bf16_p192_epi<PE_BIAS | PE_RELU | PE_DROP>(d, s);  // FFN layer 1
-      case PE_BIAS | PE_DROP | PE_RES: return launch_bf16_p192_epi<PE_BIAS | PE_DROP | PE_RES>(d, s);    // FFN layer 2, attention output
-      case PE_GATE: return launch_bf16_p192_epi<PE_GATE>(d, s);                        // gradient through ReLU + dropout
-      case PE_DOT: return launch_bf16_p192_epi<PE_DOT>(d, s);                          // attention output projection's input gradient + delta
+      case PE_BIAS | PE_LNF: return launch_p192_epi<PE_BIAS | PE_LNF>(d, s);      // q/k/v projections on the raw residual stream
+      case PE_BIAS | PE_RELU | PE_DROP | PE_LNF: return launch_p192_epi<PE_BIAS | PE_RELU | PE_DROP | PE_LNF>(d, s);  // FFN layer 1, same
+      case PE_BIAS | PE_DROP | PE_RES | PE_STATS: return launch_p192_epi<PE_BIAS | PE_DROP | PE_RES | PE_STATS>(d, s);  // + next LN's row sums
+      case PE_BIAS | PE_RELU | PE_LNF: return launch_p192_epi<PE_BIAS | PE_RELU | PE_LNF>(d, s);  // evaluation mode (no dropout)
+      case PE_BIAS | PE_RES | PE_STATS: return launch_p192_epi<PE_BIAS | PE_RES | PE_STATS>(d, s);
+      case 0: return launch_p192_epi<0>(d, s);                                    // input gradients
+      case PE_BIAS: return launch_p192_epi<PE_BIAS>(d, s);                        // q/k/v projections
+      case PE_BIAS | PE_RELU | PE_DROP: return launch_p192_epi<PE_BIAS | PE_RELU | PE_DROP>(d, s);  // FFN layer 1
+      case PE_BIAS | PE_DROP | PE_RES: return launch_p192_epi<PE_BIAS | PE_DROP | PE_RES>(d, s);    // FFN layer 2, attention output
+      case PE_GATE: return launch_p192_epi<PE_GATE>(d, s);                        // gradient through ReLU + dropout
+      case PE_DOT: return launch_p192_epi<PE_DOT>(d, s);                          // attention output projection's input gradient + delta
       default: break;
     }
   }
@@ -2933,23 +2884,14 @@ int launch_bf16_p192(const js2t_gemm_desc& d, hipStream_t s) {
                    "dot_partial: plain epilogue only");
     return JS2T_ERR_INVALID;
   }
-  return launch_bf16_p192_epi<-1>(d, s);
+  return launch_p192_epi<-1>(d, s);
 }
 
 template <int BM, bool TA, bool TB, bool SPLITK, int NST = 2>
 int launch_bf16_dma_bm(const js2t_gemm_desc& d, hipStream_t s) {
   constexpr int STAGE = ((BM == 128 || TA) ? 16384 : BM * 128) + 16384;
   constexpr int LDS = NST * STAGE > BM * 128 * 4 ? NST * STAGE : BM * 128 * 4;  // stages (the epilogue staging aliases them)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_dma_kernel<BM, TA, TB, SPLITK, NST>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE((gemm_bf16_dma_kernel<BM, TA, TB, SPLITK, NST>), LDS);
   const int tm = cdiv(d.M, BM), tn = cdiv(d.N, F_BN);
   hipLaunchKernelGGL((gemm_bf16_dma_kernel<BM, TA, TB, SPLITK, NST>), dim3(tm * tn, d.batch, SPLITK ? d.split_k : 1), dim3(256), LDS,
                      s, d, tm, tn, (float*)d.C, d.split_k);
@@ -2976,16 +2918,7 @@ int launch_bf16_impl(const js2t_gemm_desc& d, hipStream_t s) {
   constexpr int A_BYTES = TA ? TR_TILE_BYTES : KC_TILE_BYTES;
   constexpr int B_BYTES = TB ? TR_TILE_BYTES : KC_TILE_BYTES;
   constexpr int LDS = 2 * (A_BYTES + B_BYTES);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_kernel<TA, TB, SPLITK>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE((gemm_bf16_kernel<TA, TB, SPLITK>), LDS);
   const int tm = cdiv(d.M, F_BM), tn = cdiv(d.N, F_BN);
   hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, SPLITK>), dim3(tm * tn, d.batch, SPLITK ? d.split_k : 1), dim3(256), LDS, s, d,
                      tm, tn, (float*)d.C, d.split_k);
@@ -3000,8 +2933,6 @@ int launch_bf16(const js2t_gemm_desc& d, hipStream_t s) {
     return d.split_k > 1 ? launch_bf16_dma<TA, TB, true>(d, s) : launch_bf16_dma<TA, TB, false>(d, s);
   return d.split_k > 1 ? launch_bf16_impl<TA, TB, true>(d, s) : launch_bf16_impl<TA, TB, false>(d, s);
 }
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
@@ -3025,16 +2956,7 @@ extern "C" void js2t_gemm_p192_mode(int mode) { js2t_ctx_override(JS2T_CTX_GEMM_
 template <bool SPLITK>
 static int launch_grouped_tt(const js2t_gemm_desc& d, const GemmGroup& grp, int count, hipStream_t s) {
   constexpr int LDS = 65536;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_dma_grouped_kernel<128, true, true, SPLITK>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE((gemm_bf16_dma_grouped_kernel<128, true, true, SPLITK>), LDS);
   const int tm = cdiv(d.M, 128), tn = cdiv(d.N, F_BN);
   hipLaunchKernelGGL((gemm_bf16_dma_grouped_kernel<128, true, true, SPLITK>), dim3(tm * tn * count * (SPLITK ? d.split_k : 1)), dim3(256),
                      LDS, s, d, grp, tm, tn, d.split_k);
@@ -3055,18 +2977,9 @@ static bool p192t_eligible(const js2t_gemm_desc& d, int count) {
 }
 template <bool RS>
 static int launch_grouped_p192t(const js2t_gemm_desc& d, const GemmGroup& grp, int count, hipStream_t s) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_p192t_kernel<RS>, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
-    int dev = 0, cu = 0;
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu <= 0) {
-      js2t_set_error("gemm p192t setup: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    n_cu = (cu & ~7) ? (cu & ~7) : cu;
-  }
+  JS2T_LDS_ONCE(gemm_bf16_p192t_kernel<RS>, P_LDS);
+  const int n_cu = js2t_cu_count8();
+  if (n_cu <= 0) return JS2T_ERR_LAUNCH;
   const int tm = cdiv(d.M, P_BM), tn = d.N >> 7;
   const int total = tm * tn * count, grid = total < n_cu ? total : n_cu;
   hipLaunchKernelGGL(gemm_bf16_p192t_kernel<RS>, dim3(grid), dim3(256), P_LDS, s, d, grp, tm, tn, count);
@@ -3086,15 +2999,7 @@ static bool wg256_eligible(const js2t_gemm_desc& d, int count) {
 }
 template <bool RS, bool SPLITK>
 static int launch_grouped_wg256(const js2t_gemm_desc& d, const GemmGroup& grp, int count, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)(gemm_bf16_wg256_kernel<RS, SPLITK>), hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE((gemm_bf16_wg256_kernel<RS, SPLITK>), WG_LDS);
   const int tm = d.M >> 8, tn = d.N >> 7;
   hipLaunchKernelGGL((gemm_bf16_wg256_kernel<RS, SPLITK>), dim3(tm * tn * count * (SPLITK ? d.split_k : 1)), dim3(768), WG_LDS, s, d, grp, tm, tn,
                      d.split_k);
@@ -3122,21 +3027,21 @@ extern "C" int js2t_gemm_grouped(const js2t_gemm_desc* dp, int32_t count, const 
     // every tile must take the epilogue's row-segment path: whole 128-column tiles, 16-byte aligned f32 rows
     JS2T_CHECK(d.split_k == 1 && d.dtype_c == JS2T_F32 && (d.N & 127) == 0 && (d.ldc & 3) == 0,
                "gemm_grouped: sumsq_partial needs f32 C, no split-K, N % 128 == 0, ldc % 4 == 0");
-    for (int i = 0; i < count; ++i) JS2T_CHECK(aligned16(C[i]), "gemm_grouped: sumsq_partial needs 16-byte aligned C");
+    for (int i = 0; i < count; ++i) JS2T_CHECK(aligned(C[i]), "gemm_grouped: sumsq_partial needs 16-byte aligned C");
   }
   for (int base = 0; base < count; base += JS2T_GEMM_GROUP_MAX) {
     const int n = count - base < JS2T_GEMM_GROUP_MAX ? count - base : JS2T_GEMM_GROUP_MAX;
     GemmGroup grp;
     for (int i = 0; i < JS2T_GEMM_GROUP_MAX; ++i) {
       const int j = base + (i < n ? i : 0);
-      JS2T_CHECK(A[j] && B[j] && C[j] && aligned16(A[j]) && aligned16(B[j]), "gemm_grouped: operands must be non-null, 16-byte aligned");
+      JS2T_CHECK(A[j] && B[j] && C[j] && aligned(A[j]) && aligned(B[j]), "gemm_grouped: operands must be non-null, 16-byte aligned");
       grp.A[i] = A[j], grp.B[i] = B[j], grp.C[i] = C[j];
       grp.rowsum[i] = a_rowsum ? a_rowsum[j] : nullptr;
     }
     d.A = grp.A[0], d.B = grp.B[0], d.C = grp.C[0];
     int rc;
     bool c16 = true;  // (the 256x128 kernel stores 16-byte pieces)
-    for (int i = 0; i < n; ++i) c16 = c16 && aligned16(grp.C[i]);
+    for (int i = 0; i < n; ++i) c16 = c16 && aligned(grp.C[i]);
     if (c16 && wg256_eligible(d, n)) {
       if (d.split_k > 1)
         rc = a_rowsum ? launch_grouped_wg256<true, true>(d, grp, n, (hipStream_t)stream) : launch_grouped_wg256<false, true>(d, grp, n, (hipStream_t)stream);
@@ -3165,8 +3070,8 @@ extern "C" int js2t_gemm(const js2t_gemm_desc* dp, js2t_stream stream) {
   JS2T_CHECK(d.M >= 0 && d.N >= 0 && d.K >= 0 && d.batch >= 0, "gemm: negative size");
   if (d.M == 0 || d.N == 0 || d.batch == 0) return JS2T_OK;
   JS2T_CHECK(d.A && d.B && (d.C || (d.c8 && d.dtype_ab == JS2T_FP8_E4M3)), "gemm: null operand");
-  JS2T_CHECK(!d.c8 || (d.dtype_ab == JS2T_FP8_E4M3 && d.c8_state && d.ldc8 >= d.N && (d.ldc8 & 7) == 0 && (((uintptr_t)d.c8) & 7) == 0 &&
-                       (((uintptr_t)d.c8_state) & 15) == 0),
+  JS2T_CHECK(!d.c8 || (d.dtype_ab == JS2T_FP8_E4M3 && d.c8_state && d.ldc8 >= d.N && (d.ldc8 & 7) == 0 && aligned(d.c8, 8) &&
+                       aligned(d.c8_state)),
              "gemm: c8 (e4m3 second output) needs e4m3 operands, c8_state (16-byte aligned) and 8-byte aligned rows");
   JS2T_CHECK(d.batch_inner >= 1, "gemm: batch_inner must be >= 1");
   JS2T_CHECK(d.dtype_ab == JS2T_F32 || d.dtype_ab == JS2T_BF16 || d.dtype_ab == JS2T_FP8_E4M3, "gemm: bad dtype_ab");
@@ -3196,16 +3101,15 @@ extern "C" int js2t_gemm(const js2t_gemm_desc* dp, js2t_stream stream) {
                    !d.preact && d.beta == 0.f && !d.a_rowsum && !(d.residual && d.gate) && (d.act == JS2T_ACT_NONE || d.act == JS2T_ACT_RELU) &&
                    !g_force_regstage && !g_force_w256 && d.alpha == 1.f && !d.alpha_dev && d.bias,
                "gemm: ln_partial / rs_partial need a plain k-contiguous bf16 product with a bf16 result, a bias and alpha == 1");
-    JS2T_CHECK((d.N & 127) == 0 && (d.K & 7) == 0 && d.K >= 64 && (d.lda & 7) == 0 && (d.ldb & 7) == 0 && (d.ldc & 7) == 0 && aligned16(d.A) &&
-                   aligned16(d.B) && aligned16(d.C) && aligned16(d.bias) && (!d.residual || ((d.ldr & 7) == 0 && aligned16(d.residual))) &&
-                   (!d.gate || ((d.ldg & 7) == 0 && aligned16(d.gate))),
+    JS2T_CHECK((d.N & 127) == 0 && (d.K & 7) == 0 && d.K >= 64 && (d.lda & 7) == 0 && (d.ldb & 7) == 0 && aligned(d.A) && aligned(d.B) &&
+                   aligned(d.bias) && epilogue_rows_aligned(d),
                "gemm: ln_partial / rs_partial need N % 128 == 0 and 16-byte aligned rows");
     const int fmask = (d.act == JS2T_ACT_RELU ? 2 : 0) | (d.dropout_p > 0.f ? 4 : 0) | (d.residual ? 8 : 0) | (d.gate ? 16 : 0);
     JS2T_CHECK(!d.ln_partial || fmask == 0 || fmask == 2 || fmask == 6, "gemm: ln_partial: epilogue bias [+ ReLU [+ dropout]] only");
     JS2T_CHECK(!d.rs_partial || fmask == 8 || fmask == 12, "gemm: rs_partial: epilogue bias [+ dropout] + residual only");
-    JS2T_CHECK(!d.ln_partial || (d.K == 64 * LNF_GROUPS && aligned16(d.ln_partial) && d.ln_eps > 0.f && (!d.ln_mean == !d.ln_rstd)),
+    JS2T_CHECK(!d.ln_partial || (d.K == 64 * LNF_GROUPS && aligned(d.ln_partial) && d.ln_eps > 0.f && (!d.ln_mean == !d.ln_rstd)),
                "gemm: ln_partial: K must be 512 (eight 64-column groups), 16-byte aligned partial sums, ln_eps > 0, ln_mean / ln_rstd both or neither");
-    JS2T_CHECK(!d.rs_partial || (d.N == 64 * LNF_GROUPS && aligned16(d.rs_partial)), "gemm: rs_partial: N must be 512, 16-byte aligned partial sums");
+    JS2T_CHECK(!d.rs_partial || (d.N == 64 * LNF_GROUPS && aligned(d.rs_partial)), "gemm: rs_partial: N must be 512, 16-byte aligned partial sums");
   }
   if (d.dot_partial) {
     // written by the register-direct epilogues of the k-contiguous bf16 kernels (loader / consumer form of the persistent kernel,
@@ -3215,7 +3119,7 @@ extern "C" int js2t_gemm(const js2t_gemm_desc* dp, js2t_stream stream) {
                    !d.residual && !d.gate && d.alpha == 1.f && !d.alpha_dev && !d.ln_partial && !d.rs_partial && !g_force_regstage && !g_force_w256,
                "gemm: dot_partial needs a plain k-contiguous bf16 product with a bf16 result (no bias / activation / dropout / residual)");
     JS2T_CHECK((d.N & 127) == 0 && (d.K & 7) == 0 && (d.lda & 7) == 0 && (d.ldb & 7) == 0 && (d.ldc & 7) == 0 && (d.ld_dot & 7) == 0 &&
-                   aligned16(d.A) && aligned16(d.B) && aligned16(d.C) && aligned16(d.dot_src) && d.ld_dot >= d.N,
+                   aligned(d.A) && aligned(d.B) && aligned(d.C) && aligned(d.dot_src) && d.ld_dot >= d.N,
                "gemm: dot_partial needs N % 128 == 0 and 16-byte aligned rows of A, B, C and dot_src");
   }
   if (d.dtype_ab == JS2T_FP8_E4M3) {
@@ -3223,14 +3127,14 @@ extern "C" int js2t_gemm(const js2t_gemm_desc* dp, js2t_stream stream) {
     JS2T_CHECK(!d.trans_a && !d.trans_b && !d.conv && d.split_k == 1 && d.batch == 1 && d.dtype_c == JS2T_BF16 && !d.preact &&
                    d.beta == 0.f && !d.a_rowsum && !(d.residual && d.gate) && (d.act == JS2T_ACT_NONE || d.act == JS2T_ACT_RELU),
                "gemm fp8: plain k-contiguous products with a bf16 result only");
-    JS2T_CHECK((d.N & 7) == 0 && d.N >= 128 && (d.K & 15) == 0 && d.K >= 128 && (d.lda & 15) == 0 && (d.ldb & 15) == 0 && aligned16(d.A) &&
-                   aligned16(d.B) && (!d.C || aligned16(d.C)) && (d.ldc & 7) == 0,
+    JS2T_CHECK((d.N & 7) == 0 && d.N >= 128 && (d.K & 15) == 0 && d.K >= 128 && (d.lda & 15) == 0 && (d.ldb & 15) == 0 && aligned(d.A) &&
+                   aligned(d.B) && (!d.C || aligned(d.C)) && (d.ldc & 7) == 0,
                "gemm fp8: N % 8 == 0, N >= 128, K % 16 == 0, K >= 128, 16-byte aligned rows");
-    JS2T_CHECK(!d.residual || ((d.ldr & 7) == 0 && aligned16(d.residual)), "gemm fp8: misaligned residual");
-    JS2T_CHECK(!d.gate || ((d.ldg & 7) == 0 && aligned16(d.gate)), "gemm fp8: misaligned gate");
-    return launch_fp8_p192(d, s);
+    JS2T_CHECK(!d.residual || ((d.ldr & 7) == 0 && aligned(d.residual)), "gemm fp8: misaligned residual");
+    JS2T_CHECK(!d.gate || ((d.ldg & 7) == 0 && aligned(d.gate)), "gemm fp8: misaligned gate");
+    return launch_p192_epi<-1, true>(d, s);
   }
-  bool fast = d.dtype_ab == JS2T_BF16 && aligned16(d.A) && aligned16(d.B) && (d.lda % 8 == 0) && (d.ldb % 8 == 0) &&
+  bool fast = d.dtype_ab == JS2T_BF16 && aligned(d.A) && aligned(d.B) && (d.lda % 8 == 0) && (d.ldb % 8 == 0) &&
               (d.a_stride_o % 8 == 0) && (d.a_stride_i % 8 == 0) && (d.b_stride_o % 8 == 0) && (d.b_stride_i % 8 == 0) &&
               (!d.conv || d.conv_c % 8 == 0) && d.K > 0;
   if (fast) {

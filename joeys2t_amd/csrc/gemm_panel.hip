@@ -365,24 +365,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_pan96_kernel(js2t_gemm_desc 
 
 template <int EPI>
 int launch_pan96_epi(const js2t_gemm_desc& d, hipStream_t s) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_bf16_pan96_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, PN_LDS);
-    int dev = 0, cu = 0;
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu < 8) {
-      js2t_set_error("gemm pan96 setup: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    n_cu = cu & ~7;
+  JS2T_LDS_ONCE(gemm_bf16_pan96_kernel<EPI>, PN_LDS);
+  const int n_cu = js2t_cu_count8();
+  if (n_cu < 8) {  // (<= 0: the query failed and said why)
+    if (n_cu > 0) js2t_set_error("gemm pan96: %d CUs, needs at least 8", n_cu);
+    return JS2T_ERR_LAUNCH;
   }
   hipLaunchKernelGGL((gemm_bf16_pan96_kernel<EPI>), dim3(n_cu), dim3(512), PN_LDS, s, d);
   JS2T_LAUNCH_CHECK();
   return JS2T_OK;
 }
-
-inline bool al(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 
 }  // namespace
 
@@ -393,9 +385,9 @@ int launch_bf16_pan96(const js2t_gemm_desc& d, int mask, hipStream_t s) {
   if (d.dtype_ab != JS2T_BF16 || d.dtype_c != JS2T_BF16 || d.trans_a || d.trans_b || d.conv || d.split_k > 1 || d.batch != 1) return -1;
   if (d.alpha != 1.f || d.alpha_dev || d.preact || d.beta != 0.f || d.a_rowsum || d.residual || d.rs_partial || d.dot_partial || d.c8) return -1;
   if ((d.K & 127) || d.K < 128 || d.K > 64 * PN_NKMAX || (d.N & 7) || d.N < PN_COLS || d.M < PN_ROWS) return -1;
-  if (!al(d.A, 16) || !al(d.B, 16) || (d.lda & 7) || (d.ldb & 7) || !al(d.C, 8) || (d.ldc & 3)) return -1;
-  if (d.gate && (!al(d.gate, 8) || (d.ldg & 3))) return -1;
-  if (d.ln_partial && (d.K != 64 * LNF_GROUPS || !al(d.ln_partial, 16))) return -1;
+  if (!aligned(d.A) || !aligned(d.B) || (d.lda & 7) || (d.ldb & 7) || !aligned(d.C, 8) || (d.ldc & 3)) return -1;
+  if (d.gate && (!aligned(d.gate, 8) || (d.ldg & 3))) return -1;
+  if (d.ln_partial && (d.K != 64 * LNF_GROUPS || !aligned(d.ln_partial))) return -1;
   // worth it from two units per wave on (a block loads 96 KB of B before its first multiply)
   const int64_t units = (int64_t)((d.M + PN_ROWS - 1) / PN_ROWS) * ((d.N + PN_COLS - 1) / PN_COLS);
   if (g_pan_mode < 0 && units < 16 * 256) return -1;

@@ -845,12 +845,12 @@ extern "C" int js2t_ctc_bwd(const void* logits, int dt, const float* lse, const 
   }
   const size_t lds = (size_t)V * sizeof(float);
   if (dt == JS2T_F32) {
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)ctc_grad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 48 * 1024 && js2t_lds_optin((const void*)ctc_grad_kernel<float>, (int)lds) != JS2T_OK) return JS2T_ERR_LAUNCH;
     hipLaunchKernelGGL((ctc_grad_kernel<float>), dim3((unsigned)(B * T_)), dim3(LB), lds, s, (const float*)logits, lse, alpha,
                        beta, nll, targets, in_len, tgt_len, g_dev, scale, (float*)dlogits, T_, V, Lmax, Smax, blank,
                        zero_infinity, g_js2t_deterministic, row_offsets, packed_rows);
   } else {
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)ctc_grad_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 48 * 1024 && js2t_lds_optin((const void*)ctc_grad_kernel<uint16_t>, (int)lds) != JS2T_OK) return JS2T_ERR_LAUNCH;
     hipLaunchKernelGGL((ctc_grad_kernel<uint16_t>), dim3((unsigned)(B * T_)), dim3(LB), lds, s, (const uint16_t*)logits, lse,
                        alpha, beta, nll, targets, in_len, tgt_len, g_dev, scale, (uint16_t*)dlogits, T_, V, Lmax, Smax, blank,
                        zero_infinity, g_js2t_deterministic, row_offsets, packed_rows);

@@ -549,15 +549,7 @@ static int launch_ln_bwd_vec(const void* dy, const void* x, const float* gamma, 
                              int64_t nblk, int nw, size_t lds, hipStream_t s, void* dxd, float drop_p, const uint64_t* rng,
                              uint32_t rng_stream, int rows_per_block, int acc_copies, int64_t acc_stride, const float* beta,
                              void* n_out) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)layernorm_bwd_vec_kernel<T, NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE((layernorm_bwd_vec_kernel<T, NCH>), 65536);
   hipLaunchKernelGGL((layernorm_bwd_vec_kernel<T, NCH>), dim3((unsigned)nblk), dim3(64 * nw), lds, s, (const T*)dy, (const T*)x, gamma,
                      mean, rstd, (T*)dx, (const T*)add, add_scale, part, dga, dba, rows, D, (T*)dxd, drop_p, rng, rng_stream, rows_per_block, acc_copies, acc_stride,
                      beta, (T*)n_out);

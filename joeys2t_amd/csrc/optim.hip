@@ -314,15 +314,7 @@ extern "C" int js2t_adamw_items(float* p, float* g, float* exp_avg, float* exp_a
                ((uintptr_t)lp_t_bf16)) & 15) == 0, "adamw_items: buffers must be 16-byte aligned");
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)adamw_items_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ADAM_LDS);
-    if (e != hipSuccess) {
-      js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return JS2T_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  JS2T_LDS_ONCE(adamw_items_kernel, ADAM_LDS);
   hipLaunchKernelGGL(adamw_items_kernel, dim3((unsigned)n_units), dim3(256), ADAM_LDS, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq,
                      (uint16_t*)lp_bf16, (uint16_t*)lp_t_bf16, items, (int)n_items, folds, lr, beta1, beta2, eps, weight_decay,
                      (float)bc1, (float)sqrt(bc2), gscale_dev, gscale, zero_grad, lr_dev, step_dev);

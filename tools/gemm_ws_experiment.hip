@@ -263,15 +263,7 @@ extern "C" int js2t_debug_gemm_ws512(const void* X, int64_t ldx, const void* W, 
   hipStream_t s = (hipStream_t)stream;
 #define WS_LAUNCH(E)                                                                                                         \
   do {                                                                                                                       \
-    static bool attr_set = false;                                                                                            \
-    if (!attr_set) {                                                                                                         \
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_ws512_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS); \
-      if (e != hipSuccess) {                                                                                                 \
-        js2t_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));                                                     \
-        return JS2T_ERR_LAUNCH;                                                                                              \
-      }                                                                                                                      \
-      attr_set = true;                                                                                                       \
-    }                                                                                                                        \
+    JS2T_LDS_ONCE(gemm_ws512_kernel<E>, WS_LDS);                                                                             \
     hipLaunchKernelGGL(gemm_ws512_kernel<E>, grid, block, WS_LDS, s, (const uint16_t*)X, ldx, (const uint16_t*)W, ldw, (uint16_t*)C, \
                        ldc, bias, M, N, ranges, rows_per);                                                                   \
   } while (0)
