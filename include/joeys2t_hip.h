@@ -478,6 +478,29 @@ int js2t_ctc_beam_search(const void* logits, int dt, const float* lse, const int
                          int64_t B, int64_t T, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best,
                          int64_t blank, int64_t pad, const int32_t* row_offsets, js2t_stream stream);
 
+/* EXTENSION (the reference has no consumer of ctc_out, joeynmt/model.py:162-166): attention rescoring of an n-best list - the second
+ * pass of two-pass decoding.  R = B * N hypotheses (N slots per utterance, js2t_ctc_beam_search's layout) have been run through the
+ * decoder teacher-forced in ONE pass; this call turns the logits into per-token log-probabilities, sums them per hypothesis, combines
+ * the sum with the CTC score and ranks the N slots of every utterance.  Natural logarithms, f32.
+ * logits [R, Lp, V] f32 or bf16, rows V elements apart (the base address need not be 16-byte aligned: a view is fine); row (r, l) is the
+ * distribution after l labels.  ids: the labels of hypothesis r at ids + r * ids_stride (the beam kernel's [B, N, T] with ids_stride
+ * = T); n i32 [R] label counts; ctc_score f32 [R].
+ * gold(r, l) = ids[r][l] for l < n[r], eos for l == n[r] - the length decides, no id is a sentinel (a hypothesis may contain pad or
+ * eos as labels).  tok_lp[r, l] = logits[r, l, gold] - lse(logits[r, l, :]) for l <= n[r] (-inf where gold is outside 0 .. V-1) and
+ * exactly 0 behind that; att_score[r] = the sum of tok_lp[r, 0 .. n[r]] in ascending l (one fixed order: bit-reproducible, independent
+ * of the rest of the batch); score = ctc_weight * ctc_score + (1 - ctc_weight) * att_score, a term whose weight is exactly 0 LEFT OUT
+ * (ctc_weight 1 returns ctc_score's bits even where att_score is -inf, ctc_weight 0 returns att_score's).
+ * Dead slots: ctc_score = -inf (the beam kernel's "fewer than n_best prefixes"), n < 0 or n > Lp - 1: att_score = score = -inf, tok_lp
+ * all 0.  Logits of dead slots and of positions behind n[r], and ids behind n[r], are never read.
+ * order i32 [B, N]: order[b, k] = the input slot (0 .. N-1) of utterance b's k-th best by score, descending; equal scores keep slot
+ * order; a NaN score ranks as -inf (and stays NaN in `score`): order[b, :] is a permutation of 0 .. N-1 whatever the data.
+ * att_score / score [R] stay in input slot order.
+ * Limits: 1 <= N <= 32, Lp >= 1, V >= 2, 0 <= eos < V, 0 <= ctc_weight <= 1, ids_stride >= Lp - 1, B * N * Lp < 2^31; B = 0 returns 0.
+ * Two launches on `stream`; no workspace, no atomics, no allocation, no synchronisation: capturable. */
+int js2t_rescore(const void* logits, int dt, const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* ctc_score,
+                 float* tok_lp, float* att_score, float* score, int32_t* order, int64_t B, int32_t N, int64_t Lp, int64_t V,
+                 int64_t eos, float ctc_weight, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

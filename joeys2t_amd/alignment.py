@@ -38,8 +38,9 @@ def frame_seconds(model, frame_shift_ms: float = 10.0) -> float:
     return (2 ** (sub.n_layers if sub is not None else 0)) * frame_shift_ms / 1000.0
 
 
-def _ctc_frames(model, batch, who: str = "forced_align", want_lse: bool = True):
-    """(ctc logits [B, T', V], lse [B * T'] or None, input lengths i64[B]) the way search.ctc_greedy obtains them"""
+def _ctc_frames(model, batch, who: str = "forced_align", want_lse: bool = True, want_encoder: bool = False):
+    """(ctc logits [B, T', V], lse [B * T'] or None, input lengths i64[B]) the way search.ctc_greedy obtains them; with want_encoder
+    also the encoder output and its mask, for a caller that goes on to run the decoder on the same encoding"""
     from joeys2t_amd import ops
     layer = getattr(model.decoder, "ctc_output_layer", None)
     if layer is None:
@@ -49,6 +50,8 @@ def _ctc_frames(model, batch, who: str = "forced_align", want_lse: bool = True):
     B, T, V = ctc_out.shape
     lse = ops.row_lse(ctc_out.view(B * T, V))[0] if want_lse else None
     in_len = src_mask.squeeze(1).sum(dim=1).to(torch.int64).contiguous()
+    if want_encoder:
+        return ctc_out, lse, in_len, encoder_output, src_mask
     return ctc_out, lse, in_len
 
 

@@ -843,6 +843,46 @@ def ctc_beam_search(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: 
     return ids, n, score
 
 
+def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, out=None):
+    """Attention rescoring of an n-best list (js2t_rescore): logits3d [R, Lp, V] f32 / bf16, the teacher-forced decoder output of
+    R = B * N hypotheses (row l = the distribution after l labels; dense rows, any storage offset - a view is fine); ids i64
+    [B, N, T] or [R, T] (ctc_beam_search's table as it is, T >= Lp - 1), n i32 [B, N] or [R] label counts, ctc_score f32 [B, N] or [R].
+    Returns (tok_lp f32 [R, Lp]: log-probability of every gold token, EOS at position n, 0 behind it; att_score f32 [R] their sum;
+    score f32 [R] = ctc_weight * ctc_score + (1 - ctc_weight) * att_score, both in input slot order; order i32 [B, N]: the input slot
+    of every utterance's k-th best).  Dead slots (ctc_score -inf, n outside 0 .. Lp - 1): -inf scores, ranked last.
+    out: the four output tensors to write instead of fresh ones (contiguous, those shapes and dtypes)."""
+    _dev(logits3d, ids, n, ctc_score, *(out or ()))
+    if logits3d.dim() != 3:
+        raise Js2tError(f"rescore: logits [R, Lp, V] expected, got {tuple(logits3d.shape)}")
+    R, Lp, V = logits3d.shape
+    N = int(N)
+    if R and (logits3d.stride(2) != 1 or logits3d.stride(1) != V or logits3d.stride(0) != Lp * V):
+        raise Js2tError(f"rescore: logits with dense rows expected, got strides {logits3d.stride()} for {tuple(logits3d.shape)}")
+    if N < 1:  # (no [B, N] to allocate for the library to refuse)
+        raise Js2tError(f"rescore: N {N} outside 1..32")
+    if R % N:
+        raise Js2tError(f"rescore: {R} hypotheses are no multiple of N = {N}")
+    B = R // N
+    if ids.dim() not in (2, 3) or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != R * ids.shape[-1]:
+        raise Js2tError(f"rescore: contiguous i64 ids [{B}, {N}, T] expected, got {ids.dtype} {tuple(ids.shape)}")
+    if n.dtype != torch.int32 or n.numel() != R or not n.is_contiguous() or ctc_score.dtype != torch.float32 \
+            or ctc_score.numel() != R or not ctc_score.is_contiguous():
+        raise Js2tError(f"rescore: contiguous i32 lengths and f32 CTC scores of {R} hypotheses expected, got {n.dtype} "
+                        f"{tuple(n.shape)} and {ctc_score.dtype} {tuple(ctc_score.shape)}")
+    dev = logits3d.device
+    if out is None:
+        out = (torch.empty((R, Lp), dtype=torch.float32, device=dev), torch.empty((R, ), dtype=torch.float32, device=dev),
+               torch.empty((R, ), dtype=torch.float32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev))
+    else:
+        want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
+        if len(out) != 4 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
+            raise Js2tError(f"rescore: out = contiguous (f32 [{R}, {Lp}], f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
+    tok_lp, att, score, order = out
+    check(lib().js2t_rescore(_p(logits3d), dt_code(logits3d), _p(ids), ids.shape[-1], _p(n), _p(ctc_score), _p(tok_lp), _p(att), _p(score),
+                             _p(order), B, N, Lp, V, int(eos), float(ctc_weight), _stream()), "js2t_rescore")
+    return tok_lp, att, score, order
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the

@@ -20,14 +20,14 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import ctc_beam_search, search
+from joeys2t_amd.search import ctc_attention_rescore, ctc_beam_search, search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
             max_output_length: int = -1, min_output_length: int = 1, generate_unk: bool = True,
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
-            decoder: str = "attention", ctc_candidates: int = 8):
+            decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -37,10 +37,13 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     sentences in dataset order (`batch.indices`), as in the reference (prediction.py:222-231, 250-257).
     decoder="ctc" (EXTENSION): hypotheses come from the CTC output layer alone - `search.ctc_beam_search` with a beam of `beam_size`
     (any value >= 1) over the `ctc_candidates` best labels of every frame; scores (with return_prob="hyp") are the log-probabilities
-    of the labellings; the options of the attention decoder (beam_alpha, output lengths, penalties, attention) do not apply."""
-    if decoder not in ("attention", "ctc"):
-        raise ValueError(f"predict: decoder '{decoder}' is neither 'attention' nor 'ctc'")
-    ctc = decoder == "ctc"
+    of the labellings; the options of the attention decoder (beam_alpha, output lengths, penalties, attention) do not apply.
+    decoder="ctc-attention" (EXTENSION): two-pass decoding - `search.ctc_attention_rescore`: the `beam_size` best CTC hypotheses are
+    scored by the attention decoder in one teacher-forced pass and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention;
+    scores are the combined ones.  `ctc_weight` is read by this decoder only."""
+    if decoder not in ("attention", "ctc", "ctc-attention"):
+        raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
+    ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}
     totals: Dict[str, float] = {"loss": 0.0, "n_correct": 0, "ntokens": 0, "nseqs": 0}
@@ -67,7 +70,11 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             totals["loss"] += float(batch_loss.sum().item())
             totals["n_correct"] += int(n_correct.sum().item())
             totals["ntokens"] += int(batch_ntokens.sum().item())
-        if return_prob != "ref" and ctc:
+        if return_prob != "ref" and decoder == "ctc-attention":
+            ids, scores, _ = ctc_attention_rescore(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates,
+                                                   ctc_weight=ctc_weight)
+            scores = scores if return_prob == "hyp" else None
+        elif return_prob != "ref" and ctc:
             ids, scores, _ = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref":

@@ -508,3 +508,57 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     n = n.cpu().numpy().astype(np.int64).reshape(B * n_best)
     L = max(int(n.max()) if n.size else 0, 1)
     return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
+
+
+def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
+                          n_rescore: int = None, return_parts: bool = False):
+    """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
+    of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
+    over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
+    the log-probabilities of the hypothesis' labels and of EOS behind them (js2t_rescore).  The encoder runs once; the n-best list,
+    the decoder input and the scores stay on the device, with one host read (the longest hypothesis) to size the decoder pass.
+    The decoder input is [BOS, labels...] with the target mask made from the LENGTHS (a hypothesis may contain pad or EOS as labels);
+    the encoder output and its mask are tiled n_rescore times as `beam_search` does - the padded path: packed encoder rows are not
+    handed to the decoder here.
+    Returns NumPy in `ctc_beam_search`'s layout: ids i64 [B * n_best, L] pad-filled, scores f32 [B * n_best, 1] (the combined score;
+    -inf with an all-pad row where an utterance has fewer than n_best prefixes), lengths i64 [B * n_best]; with return_parts a fourth
+    element, a dict of per-returned-row NumPy data: "ctc" and "attention" f32 [B * n_best] (the two scores), "token_log_probs" (a
+    list of f32 arrays of n + 1 values, the last one EOS's) and "ctc_rank" i64 [B * n_best] (the slot of the row in the CTC n-best)."""
+    from joeys2t_amd.alignment import _ctc_frames
+    n_rescore = beam_size if n_rescore is None else n_rescore
+    beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
+    if not 1 <= n_best <= n_rescore <= beam_size <= 32:
+        raise ValueError(f"ctc_attention_rescore: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} <= 32 expected "
+                         "(all at least 1)")
+    if not 0.0 <= ctc_weight <= 1.0:  # (a NaN fails too)
+        raise ValueError(f"ctc_attention_rescore: ctc_weight {ctc_weight} outside [0, 1]")
+    N = n_rescore
+    with torch.no_grad():
+        ctc_out, _, in_len, encoder_output, src_mask = _ctc_frames(model, batch, who="ctc_attention_rescore", want_lse=False,
+                                                                   want_encoder=True)
+        B, T, V = ctc_out.shape
+        dev = ctc_out.device
+        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
+        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
+        Lp = int(n.max().item()) + 1 if n.numel() else 1  # the one host read: it sizes the decoder pass
+        ids2 = ids.view(B * N, T)
+        trg_input = torch.cat([torch.full((B * N, 1), model.bos_index, dtype=torch.int64, device=dev), ids2[:, :Lp - 1]], dim=1).contiguous()
+        trg_mask = (torch.arange(Lp, device=dev)[None, :] <= n.view(B * N, 1)).unsqueeze(1)  # [R, 1, Lp] from the lengths, not from pad ids
+        dec_logits, _, _, _ = model(return_type="decode", trg_input=trg_input, encoder_output=tile(encoder_output.contiguous(), N, dim=0),
+                                    encoder_hidden=None, src_mask=tile(src_mask, N, dim=0), unroll_steps=None, decoder_hidden=None,
+                                    trg_mask=trg_mask)
+        tok_lp, att, score, order = ops.rescore(dec_logits.contiguous(), ids, n, ctc, N, model.eos_index, ctc_weight)
+        slot = order[:, :n_best].to(torch.int64)
+        rows = (slot + torch.arange(B, device=dev)[:, None] * N).reshape(B * n_best)  # the n_best first of every utterance
+        out_n = n.view(B * N)[rows].to(torch.int64).cpu().numpy()
+        L = max(int(out_n.max()) if out_n.size else 0, 1)
+        out_ids = np.ascontiguousarray(ids2[rows].cpu().numpy()[:, :L])
+        out_score = score[rows].cpu().numpy().reshape(B * n_best, 1)
+        if not return_parts:
+            return out_ids, out_score, out_n
+        tl = tok_lp[rows].cpu().numpy()
+        parts = {"ctc": ctc.view(B * N)[rows].cpu().numpy(), "attention": att[rows].cpu().numpy(),
+                 "token_log_probs": [tl[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)],
+                 "ctc_rank": slot.reshape(B * n_best).cpu().numpy()}
+    return out_ids, out_score, out_n, parts
