@@ -501,6 +501,44 @@ int js2t_rescore(const void* logits, int dt, const int64_t* ids, int64_t ids_str
                  float* tok_lp, float* att_score, float* score, int32_t* order, int64_t B, int32_t N, int64_t Lp, int64_t V,
                  int64_t eos, float ctc_weight, js2t_stream stream);
 
+/* EXTENSION (the reference has no language model): back-off n-gram LM rescoring of an n-best list.  It sits where js2t_rescore sits
+ * and mirrors its layout and its dead-slot, weight-zero, tie and NaN rules, so that the two compose: R = B * N hypotheses, N slots per
+ * utterance; the labels of hypothesis r at ids + r * ids_stride; n i32 [R] label counts; base_score f32 [R] the first pass's score
+ * (the CTC score, or js2t_rescore's combined score).  The LM is over the target vocabulary itself.  Natural logarithms, f32.
+ * The model, a layout a C caller can build (joeys2t_amd/lm.py does; joeys2t_amd/csrc/ngram.hpp reads it):
+ *   uni f32 [V, 2]: (logp, backoff) of every id, dense.
+ *   table: `capacity` entries of 16 bytes {uint64 key, f32 logp, f32 backoff}, 16-byte aligned, holding the 2-grams .. order-grams.
+ *   Key of the k-gram (w1 .. wk): field j (0 = newest = wk) is id + 1 in bits 16j .. 16j+15: exactly k non-zero fields, 0 marks an
+ *   empty slot, and the key IS the n-gram - nothing is compared by hash, there are no false matches.  Hence order <= 4, V <= 65535.
+ *   Order 1 has no table: capacity 0, table NULL.  Home slot = fmix(key) & (capacity - 1), fmix the splitmix64 finaliser stated at
+ *   js2t_ctc_beam_search; linear probing with wrap-around; capacity a power of two.  max_probe = the largest number of slots any
+ *   stored key lies from its home, plus 1: a lookup examines slots home, home + 1, ... until it finds the key, finds an empty slot
+ *   or has examined max_probe slots - stopping there is exact.
+ * Token rule: gold(r, l) = ids[r][l] for l < n[r], eos for l == n[r] - the length decides, no id is a sentinel.  The history of
+ * position l is (bos, ids[r][0 .. l-1]); its last order - 1 tokens are the context, cut behind the newest id outside 0 .. V-1 (only
+ * the tokens after it count).
+ * Back-off rule: acc = 0; for k = (context length) down to 1: if the (k+1)-gram (context's last k, w) is stored, the value is acc +
+ * its logp; otherwise acc += the back-off of the k-gram (context's last k) if that is stored, else 0 (for k = 1 that is uni[c][1]).
+ * With no match the value is acc + uni[w][0].  w outside 0 .. V-1: -inf.  acc is summed in f32 from the longest context down.
+ * lm_tok f32 [R, Lp] (may be NULL: then nothing is stored and Lp only bounds n): the values for l <= n[r], exactly 0 behind.
+ * lm_score[r] = their sum in ONE fixed order that depends on n[r] alone (the same bits alone and in a batch, on every run, under
+ * graph replay, with and without lm_tok).  score = base_score + lm_weight * lm_score + length_bonus * n[r], each product rounded to
+ * f32, added in that order; a term whose weight is exactly 0 is LEFT OUT: lm_weight 0 and length_bonus 0 return base_score's bits.
+ * With lm_weight exactly 0 the model is left out altogether: uni and table are not read (both may be NULL, capacity 0), lm_tok is
+ * all 0 and lm_score is 0 for live slots.
+ * Dead slots: base_score = -inf, n < 0 or n > Lp - 1: lm_score = score = -inf, lm_tok all 0, none of their ids read.  Ids behind
+ * n[r] are never read.
+ * order i32 [B, N]: order[b, k] = the input slot of utterance b's k-th best by score, descending; equal scores keep slot order; a
+ * NaN score ranks as -inf (and stays NaN in `score`): always a permutation of 0 .. N-1.  lm_score / score [R] stay in slot order.
+ * Limits: 1 <= N <= 32, 1 <= lm_order <= 4, 2 <= V <= 65535, 0 <= bos, eos < V, Lp >= 1, ids_stride >= Lp - 1, B * N * Lp < 2^31,
+ * capacity 0 or a power of two, 1 <= max_probe <= capacity when lm_order > 1 (and lm_weight != 0), lm_weight and length_bonus
+ * finite; B = 0 returns 0.
+ * Two launches on `stream`; no workspace, no atomics, no allocation, no synchronisation: capturable. */
+int js2t_ngram_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* base_score, const float* uni,
+                       const void* table, int64_t capacity, int32_t max_probe, int32_t lm_order, float* lm_tok, float* lm_score,
+                       float* score, int32_t* order, int64_t B, int32_t N, int64_t Lp, int64_t V, int64_t bos, int64_t eos,
+                       float lm_weight, float length_bonus, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

@@ -883,6 +883,62 @@ def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, ou
     return tok_lp, att, score, order
 
 
+def ngram_rescore(ids, n, base_score, N: int, lm, bos: int, eos: int, lm_weight: float, length_bonus: float, Lp: int = None,
+                  want_tokens: bool = False, out=None, V: int = None):
+    """N-gram LM rescoring of an n-best list (js2t_ngram_rescore): ids i64 [B, N, T] or [R, T] (ctc_beam_search's table as it is),
+    n i32 [B, N] or [R] label counts, base_score f32 [B, N] or [R] the first pass's score (the CTC score, or rescore's combined
+    one); lm: a joeys2t_amd.lm.NGramLM on the tensors' device, or None when lm_weight is 0 (then V is given).  Lp bounds the lengths
+    (a slot with n > Lp - 1 is dead) and is lm_tok's row length; default T + 1, which no length exceeds - no host read is needed.
+    Returns (lm_tok f32 [R, Lp] or None without want_tokens: log-probability of every token, EOS at position n, 0 behind it;
+    lm_score f32 [R] their sum; score f32 [R] = base_score + lm_weight * lm_score + length_bonus * n, a term of weight 0 left out, both
+    in input slot order; order i32 [B, N]: the input slot of every utterance's k-th best).  Dead slots (base_score -inf, n outside
+    0 .. Lp - 1): -inf scores, ranked last.
+    out: the output tensors to write instead of fresh ones: (lm_tok or None, lm_score, score, order), contiguous."""
+    _dev(ids, n, base_score, *(t for t in (out or ()) if t is not None))
+    N = int(N)
+    if N < 1:  # (no [B, N] to allocate for the library to refuse)
+        raise Js2tError(f"ngram_rescore: N {N} outside 1..32")
+    if ids.dim() not in (2, 3) or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise Js2tError(f"ngram_rescore: contiguous i64 ids [B, {N}, T] expected, got {ids.dtype} {tuple(ids.shape)}")
+    T = ids.shape[-1]
+    R = ids.numel() // T if T else n.numel()
+    if R % N:
+        raise Js2tError(f"ngram_rescore: {R} hypotheses are no multiple of N = {N}")
+    B = R // N
+    if n.dtype != torch.int32 or n.numel() != R or not n.is_contiguous() or base_score.dtype != torch.float32 \
+            or base_score.numel() != R or not base_score.is_contiguous():
+        raise Js2tError(f"ngram_rescore: contiguous i32 lengths and f32 scores of {R} hypotheses expected, got {n.dtype} "
+                        f"{tuple(n.shape)} and {base_score.dtype} {tuple(base_score.shape)}")
+    Lp = T + 1 if Lp is None else int(Lp)
+    dev = ids.device
+    if lm is None:
+        if float(lm_weight) != 0.0 or V is None:
+            raise Js2tError("ngram_rescore: without an lm, lm_weight 0 and V expected")
+        uni = table = None
+        capacity, max_probe, order_lm = 0, 1, 1
+    else:
+        if lm.uni_dev is None or lm.uni_dev.device != dev:
+            raise Js2tError(f"ngram_rescore: the lm is on {lm.device}, the hypotheses on {dev}: lm.to(device) first")
+        if V is not None and int(V) != lm.V:
+            raise Js2tError(f"ngram_rescore: the lm is over {lm.V} ids, V = {V}")
+        uni, table, V = lm.uni_dev, (lm.table_dev if lm.capacity else None), lm.V
+        capacity, max_probe, order_lm = lm.capacity, lm.max_probe, lm.order
+    if out is None:
+        out = (torch.empty((R, max(Lp, 0)), dtype=torch.float32, device=dev) if want_tokens else None,
+               torch.empty((R, ), dtype=torch.float32, device=dev), torch.empty((R, ), dtype=torch.float32, device=dev),
+               torch.empty((B, N), dtype=torch.int32, device=dev))
+    else:
+        want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
+        given = [(t, w) for t, w in zip(out, want) if t is not None or w is not want[0]]  # lm_tok alone may be None
+        if len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in given):
+            raise Js2tError(f"ngram_rescore: out = contiguous (f32 [{R}, {Lp}] or None, f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
+    lm_tok, lm_score, score, order = out
+    check(lib().js2t_ngram_rescore(_p(ids), T, _p(n), _p(base_score), _p(uni), _p(table), capacity, max_probe, order_lm, _p(lm_tok),
+                                   _p(lm_score), _p(score), _p(order), B, N, Lp, int(V), int(bos), int(eos), float(lm_weight),
+                                   float(length_bonus), _stream()), "js2t_ngram_rescore")
+    return lm_tok, lm_score, score, order
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the

@@ -27,7 +27,8 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             max_output_length: int = -1, min_output_length: int = 1, generate_unk: bool = True,
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
-            decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3):
+            decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
+            length_bonus: float = 0.0):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -40,9 +41,17 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     of the labellings; the options of the attention decoder (beam_alpha, output lengths, penalties, attention) do not apply.
     decoder="ctc-attention" (EXTENSION): two-pass decoding - `search.ctc_attention_rescore`: the `beam_size` best CTC hypotheses are
     scored by the attention decoder in one teacher-forced pass and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention;
-    scores are the combined ones.  `ctc_weight` is read by this decoder only."""
+    scores are the combined ones.  `ctc_weight` is read by this decoder only.
+    lm / lm_weight / length_bonus (EXTENSION): an n-gram LM over the target vocabulary (joeys2t_amd.lm.NGramLM) and a bonus per label,
+    handed to the two CTC decoders, which re-rank their n-best list with them on the device; the attention decoder has no place
+    for them and refuses them."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
+    if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
+        raise ValueError("predict: lm / lm_weight / length_bonus re-rank the n-best list of decoder='ctc' or 'ctc-attention'; "
+                         "decoder='attention' cannot apply them")
+    lm_kw = {} if lm is None and float(lm_weight) == 0.0 and float(length_bonus) == 0.0 else \
+        dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
     ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}
@@ -72,10 +81,10 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             totals["ntokens"] += int(batch_ntokens.sum().item())
         if return_prob != "ref" and decoder == "ctc-attention":
             ids, scores, _ = ctc_attention_rescore(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates,
-                                                   ctc_weight=ctc_weight)
+                                                   ctc_weight=ctc_weight, **lm_kw)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref" and ctc:
-            ids, scores, _ = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates)
+            ids, scores, _ = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates, **lm_kw)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref":
             ids, scores, att = search(model=model, batch=batch, beam_size=beam_size, beam_alpha=beam_alpha, n_best=n_best,

@@ -17,6 +17,7 @@ between those stages, so with any of them on the step runs as js2t_log_softmax -
     to 0 AFTER the forbidden ids were masked; the prompt mask is embedded and added to the decoder input (model.py:271-282),
     which needs the full-prefix decoder pass (no KV cache on this path);
   * `return_attention` (greedy only, :318-325): cross-attention weights of the last layer, full-prefix pass."""
+import math
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -488,16 +489,46 @@ def ctc_greedy(model, batch):
 
 
 
-def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8):
+def _ngram_args(who, lm, lm_weight, length_bonus):
+    """(re-rank at all?, lm_weight, length_bonus) of the LM options of the two CTC decoders; refused before the model is touched"""
+    lm_weight, length_bonus = float(lm_weight), float(length_bonus)
+    if not (math.isfinite(lm_weight) and math.isfinite(length_bonus)):
+        raise ValueError(f"{who}: lm_weight {lm_weight} / length_bonus {length_bonus} not finite")
+    if lm is None and lm_weight != 0.0:
+        raise ValueError(f"{who}: lm_weight {lm_weight} without an lm")
+    return lm is not None or length_bonus != 0.0, lm_weight, length_bonus
+
+
+def _ngram_rerank(model, ids, n, base, N, lm, lm_weight, length_bonus, dev, **kw):
+    """ops.ngram_rescore of the beam kernel's [B, N, T] table over the model's vocabulary, the lm moved to the device if need be"""
+    if lm is not None and lm.device != dev:
+        lm.to(dev)
+    return ops.ngram_rescore(ids, n, base, N, lm, model.bos_index, model.eos_index, lm_weight, length_bonus, V=len(model.trg_vocab), **kw)
+
+
+def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
+                    length_bonus: float = 0.0, n_rescore: int = None):
     """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
     `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
     `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
     Returns NumPy in the row layout of `beam_search`: ids i64 [B * n_best, L] pad-filled (L = the longest hypothesis, at least 1),
     scores f32 [B * n_best, 1] (log-probability of the labelling under the truncated distribution; -inf with an all-pad row where
-    an utterance has fewer than n_best prefixes) and lengths i64 [B * n_best]."""
+    an utterance has fewer than n_best prefixes) and lengths i64 [B * n_best].
+    With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus`, the `n_rescore` (default:
+    beam_size) best prefixes are searched for, re-ranked on the device by ctc + lm_weight * lm + length_bonus * n, lm = the LM's
+    log-probability of the labels and of EOS behind them (js2t_ngram_rescore), and the n_best first are returned with that score;
+    there is no host read between the encoder and the final copy.  Without either the search runs as it always did."""
     from joeys2t_amd.alignment import _ctc_frames
+    rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
     if not 1 <= n_best <= beam_size:
         raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
+    if rerank:
+        n_rescore = int(beam_size if n_rescore is None else n_rescore)
+        if not n_best <= n_rescore <= beam_size:
+            raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
+        return _ctc_beam_search_lm(model, batch, int(beam_size), int(n_best), candidates, lm, lm_weight, length_bonus, n_rescore)
+    if n_rescore is not None:
+        raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
     with torch.no_grad():
         ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
         B, T, V = ctc_out.shape
@@ -510,8 +541,27 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
 
 
+def _ctc_beam_search_lm(model, batch, beam_size, n_best, candidates, lm, lm_weight, length_bonus, N):
+    """ctc_beam_search with the N best prefixes re-ranked by the n-gram LM and the length bonus; the same return layout"""
+    from joeys2t_amd.alignment import _ctc_frames
+    with torch.no_grad():
+        ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
+        B, T, V = ctc_out.shape
+        dev = ctc_out.device
+        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
+        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
+        _, _, score, order = _ngram_rerank(model, ids, n, ctc, N, lm, lm_weight, length_bonus, dev)  # Lp = T + 1: no length to read
+        rows = (order[:, :n_best].to(torch.int64) + torch.arange(B, device=dev)[:, None] * N).reshape(B * n_best)
+        ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score[rows]
+    n = n.cpu().numpy().astype(np.int64)
+    L = max(int(n.max()) if n.size else 0, 1)
+    return np.ascontiguousarray(ids.cpu().numpy()[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
+
+
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
-                          n_rescore: int = None, return_parts: bool = False):
+                          n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
+                          length_bonus: float = 0.0):
     """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
     of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
     over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
@@ -523,8 +573,12 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     Returns NumPy in `ctc_beam_search`'s layout: ids i64 [B * n_best, L] pad-filled, scores f32 [B * n_best, 1] (the combined score;
     -inf with an all-pad row where an utterance has fewer than n_best prefixes), lengths i64 [B * n_best]; with return_parts a fourth
     element, a dict of per-returned-row NumPy data: "ctc" and "attention" f32 [B * n_best] (the two scores), "token_log_probs" (a
-    list of f32 arrays of n + 1 values, the last one EOS's) and "ctc_rank" i64 [B * n_best] (the slot of the row in the CTC n-best)."""
+    list of f32 arrays of n + 1 values, the last one EOS's) and "ctc_rank" i64 [B * n_best] (the slot of the row in the CTC n-best).
+    With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus` the final score is
+    ctc_weight * ctc + (1 - ctc_weight) * attention + lm_weight * lm + length_bonus * n: js2t_rescore's combined score is the base
+    score of js2t_ngram_rescore, whose ranking decides; the parts gain "lm" f32 [B * n_best] and "lm_token_log_probs"."""
     from joeys2t_amd.alignment import _ctc_frames
+    rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
     n_rescore = beam_size if n_rescore is None else n_rescore
     beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
     if not 1 <= n_best <= n_rescore <= beam_size <= 32:
@@ -549,6 +603,9 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
                                     encoder_hidden=None, src_mask=tile(src_mask, N, dim=0), unroll_steps=None, decoder_hidden=None,
                                     trg_mask=trg_mask)
         tok_lp, att, score, order = ops.rescore(dec_logits.contiguous(), ids, n, ctc, N, model.eos_index, ctc_weight)
+        if rerank:
+            lm_tok, lm_score, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, dev, Lp=Lp,
+                                                           want_tokens=return_parts)
         slot = order[:, :n_best].to(torch.int64)
         rows = (slot + torch.arange(B, device=dev)[:, None] * N).reshape(B * n_best)  # the n_best first of every utterance
         out_n = n.view(B * N)[rows].to(torch.int64).cpu().numpy()
@@ -561,4 +618,8 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         parts = {"ctc": ctc.view(B * N)[rows].cpu().numpy(), "attention": att[rows].cpu().numpy(),
                  "token_log_probs": [tl[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)],
                  "ctc_rank": slot.reshape(B * n_best).cpu().numpy()}
+        if rerank:
+            ll = lm_tok[rows].cpu().numpy()
+            parts["lm"] = lm_score[rows].cpu().numpy()
+            parts["lm_token_log_probs"] = [ll[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)]
     return out_ids, out_score, out_n, parts
