@@ -539,6 +539,37 @@ int js2t_ngram_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n,
                        float* score, int32_t* order, int64_t B, int32_t N, int64_t Lp, int64_t V, int64_t bos, int64_t eos,
                        float lm_weight, float length_bonus, js2t_stream stream);
 
+/* EXTENSION (the reference has no language model): CTC prefix beam search with n-gram LM shallow fusion INSIDE the beam.  Rescoring
+ * (js2t_ngram_rescore) can only re-order the prefixes the CTC-only beam kept; here the LM takes part in the pruning of every frame.
+ * The arguments of js2t_ctc_beam_search, the model as js2t_ngram_rescore takes it (uni, table, capacity, max_probe, lm_order; the LM
+ * is over the V ids of the logits), bos / eos / lm_weight / length_bonus, and two more outputs.  Same workspace
+ * (js2t_ctc_beam_workspace_bytes).  Natural logarithms, f32.
+ * CTC recursion, candidates, prefix identity and tie rule: exactly js2t_ctc_beam_search's; pb / pnb stay pure CTC masses.
+ * LM value: every prefix y carries lm(y), f32: lm(()) = 0, lm(y+c) = lm(y) + logp(c | last lm_order - 1 tokens of (bos, y)) under
+ * js2t_ngram_rescore's token and back-off rules.  lm(y) is the ascending sum, a function of the sequence alone: a prefix that was
+ * pruned and is created again carries the bits of its surviving twin, so contributions that reach one sequence still add up.
+ * Ranking key of a frame: key(y) = lae(pb, pnb) + lm_weight * lm(y) + length_bonus * |y|, each product rounded to f32, added in that
+ * order, a term whose weight is exactly 0 LEFT OUT (js2t_ngram_rescore's rule); the `beam` largest keys form the next beam.  With
+ * lm_weight != 0 an extension whose lm value is -inf or NaN (a label the model forbids) is not proposed.
+ * Final score, after frame T_b - 1: final(y) = lae(pb, pnb) + lm_weight * (lm(y) + logp(eos | y)) + length_bonus * |y|; the beam is
+ * ranked again by final (equal finals keep the beam's order, a NaN ranks as -inf) and the n_best first are returned.
+ * out_ids / out_len as in js2t_ctc_beam_search; out_score f32 [B, n_best] = final, out_ctc f32 [B, n_best] = lae(pb, pnb), out_lm f32
+ * [B, n_best] = lm(y) + logp(eos | y), which is 0 when lm_weight == 0.  A slot without a prefix: -inf / -inf / -inf, length 0, all pad.
+ * The result is what js2t_ngram_rescore gives the same labelling with base_score = out_ctc, up to rounding: the order of summation
+ * differs, so the two agree within the tolerance of accumulated log-likelihoods, not bitwise.
+ * T_b = 0: the empty hypothesis with final = lm_weight * logp(eos | bos).  lm_weight == 0: uni / table are not read and may be NULL.
+ * lm_weight == 0 and length_bonus == 0: ids, lengths and scores are the bits of js2t_ctc_beam_search.
+ * Limits: those of the two calls together - 1 <= beam <= 32, 1 <= n_cand <= 8, 1 <= n_best <= beam, beam * T < 2^31, 1 <= lm_order
+ * <= 4, 2 <= V <= 65535, 0 <= bos, eos < V (blank == bos is allowed), lm_weight and length_bonus finite, capacity 0 or a power of two,
+ * 1 <= max_probe <= capacity when lm_order > 1 (and lm_weight != 0); B = 0 returns 0.
+ * One launch; no atomics, no allocation, no synchronisation: bit-reproducible, capturable. */
+int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+                            const int64_t* in_len, const float* uni, const void* table, int64_t capacity, int32_t max_probe,
+                            int32_t lm_order, int64_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
+                            void* workspace, int64_t B, int64_t T, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best,
+                            int64_t blank, int64_t pad, int64_t bos, int64_t eos, float lm_weight, float length_bonus,
+                            const int32_t* row_offsets, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

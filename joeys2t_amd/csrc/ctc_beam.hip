@@ -12,7 +12,17 @@
 //
 // No atomics, no allocation, no host synchronisation; every trie node has a fixed slot (1 + t K + rank), so nothing is counted and
 // nothing read from the workspace that this launch has not written: bit-reproducible, capturable.
+//
+// LM shallow fusion (js2t_ctc_beam_search_lm) is the same kernel body with LM = true: every prefix carries lm(y), the ascending f32
+// sum of ngram.hpp's token values, and the two tokens in front of its last one (the LM's context); the frame's ranking key gains
+// lm_weight * lm(y) + length_bonus * |y| while pb / pnb / tot stay pure CTC masses.  An extension's thread computes its own
+// ngram_token_logp in phase A - five independent first probes issued together, one memory latency; a probe that meets another key
+// walks on as ngram.hpp says, and those walks are most of what the LM costs a frame - and there is no further
+// barrier and no other global traffic per frame.  After the last frame one wave adds the EOS term,
+// ranks the beam again by counting and the back-trace runs in that order.  With LM = false none of it is compiled: that form is
+// what js2t_ctc_beam_search launches.
 #include "common.hpp"
+#include "ngram.hpp"
 
 namespace {
 
@@ -44,19 +54,50 @@ __device__ __forceinline__ float cb_lae(float a, float b) {
 // comes before nothing.
 __device__ __forceinline__ int cb_before(float kp, int ep, float k, int e) { return (kp > k || (kp == k && ep < e)) ? 1 : 0; }
 
-struct CbBeam {  // one of the two beams; slot = rank of the prefix (score descending)
+template <bool LM>
+struct CbBeam {  // one of the two beams; slot = rank of the prefix (key descending)
   float pb[CB_MAX_K], pnb[CB_MAX_K], tot[CB_MAX_K];  // log-mass ending in blank / in non-blank, and their logaddexp
   uint64_t hash[CB_MAX_K], phash[CB_MAX_K];         // of the prefix, and of the prefix without its last token
   int len[CB_MAX_K], last[CB_MAX_K], node[CB_MAX_K];
+  float lm[LM ? CB_MAX_K : 1];                      // LM only: lm(y), and the second and third newest tokens of (bos, y), -1 = none
+  int t1[LM ? CB_MAX_K : 1], t2[LM ? CB_MAX_K : 1];
 };
 
-template <typename T>
+struct CbFuse {  // what the LM form takes besides the search's own arguments
+  ngram_view lm;
+  int bos, eos;
+  float lm_weight, length_bonus;
+  float *out_ctc, *out_lm;
+};
+
+// ctc + lm_weight * lm + length_bonus * len, each product rounded to f32 and added in that order, a term of weight 0 left out
+// (js2t_ngram_rescore's rule)
+__device__ __forceinline__ float cb_fuse(float ctc, float lm, int len, float lm_weight, float length_bonus) {
+#pragma clang fp contract(off)
+  float s = ctc;
+  if (lm_weight != 0.f) s += lm_weight * lm;
+  if (length_bonus != 0.f) s += length_bonus * (float)len;
+  return s;
+}
+
+// log p(w | (bos, y)) for the prefix y in slot i of the beam
+template <bool LM>
+__device__ __forceinline__ float cb_token_logp(const CbFuse& f, const CbBeam<LM>& g, int i, int w) {
+  const int len = g.len[i];
+  const int64_t c[NGRAM_MAX_CTX] = {len > 0 ? g.last[i] : f.bos, g.t1[i], g.t2[i]};
+  return ngram_token_logp(f.lm, w, c, len + 1 < NGRAM_MAX_CTX ? len + 1 : NGRAM_MAX_CTX);
+}
+
+template <typename T, bool LM>
 __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
     const T* __restrict__ x, const float* __restrict__ lse, const int64_t* __restrict__ cand_id, const float* __restrict__ cand_lp,
     const int64_t* __restrict__ in_len, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_len, float* __restrict__ out_score,
     int2* __restrict__ nodes_all, int64_t Tmax, int64_t V, int K, int C, int n_best, int blank, int64_t pad,
-    const int32_t* __restrict__ rowoff) {
-  __shared__ CbBeam beam[2];
+    const int32_t* __restrict__ rowoff, const CbFuse fuse) {
+  __shared__ CbBeam<LM> beam[2];
+  __shared__ float s_elm[LM ? CB_MAX_E : 1];            // LM only: lm(y) of every proposal of the frame
+  __shared__ int s_ord[LM ? CB_MAX_K : 1];              // LM only: beam slot of the k-th best by the final score
+  __shared__ float s_fin[LM ? CB_MAX_K : 1], s_lmf[LM ? CB_MAX_K : 1];  // final score and lm(y) + p(eos | y) per beam slot
   __shared__ __align__(16) float s_key[CB_MAX_E];       // score of every proposal of the frame, NaN where there is none
   __shared__ float s_epb[CB_MAX_E], s_epnb[CB_MAX_E];   // its two masses
   __shared__ int s_cid[CB_CHUNK][CB_MAX_C];
@@ -68,10 +109,11 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
   int2* nodes = nodes_all + (int64_t)b * (1 + (int64_t)K * Tmax);     // (parent node, token); node 0 = the empty prefix, never read
   const float nan = __int_as_float(0x7fc00000);
   if (tid == 0) {
-    CbBeam& g = beam[0];
+    CbBeam<LM>& g = beam[0];
     g.pb[0] = 0.f, g.pnb[0] = -INFINITY, g.tot[0] = 0.f;
     g.hash[0] = CB_ROOT_HASH, g.phash[0] = 0;
     g.len[0] = 0, g.last[0] = -1, g.node[0] = 0;
+    if constexpr (LM) g.lm[0] = 0.f, g.t1[0] = -1, g.t2[0] = -1;
   }
   int cur = 0, nbeam = 1;
   __syncthreads();
@@ -92,13 +134,15 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
     }
     __syncthreads();
     for (int tt = 0; tt < nt; ++tt) {  // (block-uniform bounds: nt)
-      const CbBeam& g = beam[cur];
-      CbBeam& gn = beam[cur ^ 1];
+      const CbBeam<LM>& g = beam[cur];
+      CbBeam<LM>& gn = beam[cur ^ 1];
       const int nlive = K + nbeam * C, npad = (nlive + 3) & ~3;  // proposals 0 .. K-1 stay, K + i C + s extends prefix i by slot s
       const float lpb = s_lpb[tt];
       // ---- phase A: the proposals
-      for (int e = tid; e < npad; e += CB_THREADS) {
-        float npb = -INFINITY, npnb = -INFINITY, key = nan;
+      for (int q = tid; q < npad; q += CB_THREADS) {
+        // LM: the extensions (at most 256) come first, one thread each, so that all their probes are in flight together
+        const int e = !LM ? q : q < npad - K ? q + K : q - (npad - K);
+        float npb = -INFINITY, npnb = -INFINITY, key = nan, elm = 0.f;
         if (e < nbeam) {  // prefix e stays: blank, a repeat of its last label, and the extension of its parent that recreates it
           const int last = g.last[e], len = g.len[e];
           npb = g.tot[e] + lpb;
@@ -112,6 +156,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
               if (g.len[i] + 1 == len && g.hash[i] == ph) npnb = cb_lae(npnb, (g.last[i] == last ? g.pb[i] : g.tot[i]) + lp_rep);
           }
           key = cb_lae(npb, npnb);
+          if constexpr (LM) elm = g.lm[e], key = cb_fuse(key, elm, len, fuse.lm_weight, fuse.length_bonus);
         } else if (e >= K && e < nlive) {
           const int i = (e - K) / C, s = (e - K) - i * C;
           const int c = s_cid[tt][s];
@@ -123,13 +168,21 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
             const uint64_t h = g.hash[i];
             for (int j = 0; j < nbeam; ++j)  // the beam holds this very sequence: its stay proposal has taken the mass
               if (g.len[j] == len1 && g.last[j] == c && g.phash[j] == h) ok = false;
+            if constexpr (LM) {
+              if (ok && fuse.lm_weight != 0.f) {
+                elm = g.lm[i] + cb_token_logp(fuse, g, i, c);
+                ok = elm > -INFINITY;  // an extension the LM forbids (-inf, or NaN) is not proposed
+              }
+            }
             if (ok) {
               npnb = base + s_clp[tt][s];
               key = npnb;
+              if constexpr (LM) key = cb_fuse(key, elm, len1, fuse.lm_weight, fuse.length_bonus);
             }
           }
         }
         s_key[e] = key, s_epb[e] = npb, s_epnb[e] = npnb;
+        if constexpr (LM) s_elm[e] = elm;
       }
       __syncthreads();
       // ---- phase B: rank by counting, the K first become the next beam
@@ -145,10 +198,17 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
           nv += (v.x == v.x ? 1 : 0) + (v.y == v.y ? 1 : 0) + (v.z == v.z ? 1 : 0) + (v.w == v.w ? 1 : 0);
         }
         if (k == k && rank < K) {
-          gn.pb[rank] = s_epb[e], gn.pnb[rank] = s_epnb[e], gn.tot[rank] = k;
+          gn.pb[rank] = s_epb[e], gn.pnb[rank] = s_epnb[e];
+          if constexpr (LM) {  // the key is no longer the CTC total: an extension's is its pnb, a stay's is recomputed
+            gn.tot[rank] = e < K ? cb_lae(s_epb[e], s_epnb[e]) : s_epnb[e];
+            gn.lm[rank] = s_elm[e];
+          } else {
+            gn.tot[rank] = k;
+          }
           if (e < K) {
             gn.hash[rank] = g.hash[e], gn.phash[rank] = g.phash[e];
             gn.len[rank] = g.len[e], gn.last[rank] = g.last[e], gn.node[rank] = g.node[e];
+            if constexpr (LM) gn.t1[rank] = g.t1[e], gn.t2[rank] = g.t2[e];
           } else {
             const int i = (e - K) / C, s = (e - K) - i * C;
             const int c = s_cid[tt][s];
@@ -156,6 +216,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
             gn.hash[rank] = cb_mix(g.hash[i], c), gn.phash[rank] = g.hash[i];
             gn.len[rank] = g.len[i] + 1, gn.last[rank] = c, gn.node[rank] = node;
             nodes[node] = make_int2(g.node[i], c);
+            if constexpr (LM) gn.t1[rank] = g.len[i] > 0 ? g.last[i] : fuse.bos, gn.t2[rank] = g.t1[i];
           }
         }
       }
@@ -166,25 +227,78 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
   }
   // the beam is in score order already: its first n_best slots are the result; the barrier that closed the last frame made it, and
   // the nodes (workgroup scope), visible
-  const CbBeam& g = beam[cur];
+  const CbBeam<LM>& g = beam[cur];
+  if constexpr (LM) {
+    // the EOS term and the final score, lanes < nbeam of the first wave; ranked again by counting (equal finals keep the beam's
+    // order, a NaN ranks as -inf); the back-trace below runs in that order
+    if (tid < 64) {  // (wave-uniform)
+      const bool have = tid < nbeam;
+      float lmf = 0.f, fin = -INFINITY;
+      if (have) {
+        if (fuse.lm_weight != 0.f) lmf = g.lm[tid] + cb_token_logp(fuse, g, tid, fuse.eos);
+        fin = cb_fuse(g.tot[tid], lmf, g.len[tid], fuse.lm_weight, fuse.length_bonus);
+      }
+      const float key = fin == fin ? fin : -INFINITY;
+      int rank = 0;
+      for (int j = 0; j < nbeam; ++j) {  // (block-uniform bounds)
+        const float kj = __shfl(key, j, 64);
+        rank += (kj > key || (kj == key && j < tid)) ? 1 : 0;
+      }
+      if (have) s_ord[rank] = tid, s_fin[tid] = fin, s_lmf[tid] = lmf;
+    }
+    __syncthreads();
+  }
   int64_t* oi = out_ids + (int64_t)b * n_best * Tmax;
   for (int64_t idx = tid; idx < (int64_t)n_best * Tmax; idx += CB_THREADS) {
     const int n = (int)(idx / Tmax);
-    if (n >= nbeam || idx - n * Tmax >= g.len[n]) oi[idx] = pad;
+    if (n >= nbeam || idx - n * Tmax >= g.len[LM ? s_ord[n] : n]) oi[idx] = pad;
   }
   if (tid < n_best) {
     const bool have = tid < nbeam;
-    out_score[(int64_t)b * n_best + tid] = have ? g.tot[tid] : -INFINITY;
-    out_len[(int64_t)b * n_best + tid] = have ? g.len[tid] : 0;
+    const int from = have && LM ? s_ord[tid] : tid;  // the beam slot returned in output slot tid
+    if constexpr (LM) {
+      out_score[(int64_t)b * n_best + tid] = have ? s_fin[from] : -INFINITY;
+      fuse.out_ctc[(int64_t)b * n_best + tid] = have ? g.tot[from] : -INFINITY;
+      fuse.out_lm[(int64_t)b * n_best + tid] = have ? s_lmf[from] : -INFINITY;
+    } else {
+      out_score[(int64_t)b * n_best + tid] = have ? g.tot[tid] : -INFINITY;
+    }
+    out_len[(int64_t)b * n_best + tid] = have ? g.len[from] : 0;
     if (have) {
-      int node = g.node[tid];
-      for (int p = g.len[tid] - 1; p >= 0; --p) {
+      int node = g.node[from];
+      for (int p = g.len[from] - 1; p >= 0; --p) {
         const int2 nd = nodes[node];
         oi[(int64_t)tid * Tmax + p] = nd.y;
         node = nd.x;
       }
     }
   }
+}
+
+// the checks the two entry points share, and the launch; `who` names the entry point in the messages
+template <bool LM>
+int cb_launch(const char* who, const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+              const int64_t* in_len, int64_t* out_ids, int32_t* out_len, float* out_score, void* workspace, int64_t B, int64_t T_, int64_t V,
+              int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank, int64_t pad, const int32_t* row_offsets, const CbFuse& fuse,
+              js2t_stream stream) {
+  JS2T_CHECK(logits && lse && cand_id && cand_lp && in_len && out_ids && out_len && out_score && workspace, "%s: null pointer", who);
+  JS2T_CHECK(B > 0 && T_ > 0 && V > 0 && V < 0x7fffffff, "%s: bad shape", who);
+  JS2T_CHECK(beam >= 1 && beam <= CB_MAX_K, "%s: beam %d outside 1..%d", who, (int)beam, CB_MAX_K);
+  JS2T_CHECK(n_cand >= 1 && n_cand <= CB_MAX_C, "%s: %d candidates outside 1..%d", who, (int)n_cand, CB_MAX_C);
+  JS2T_CHECK(n_best >= 1 && n_best <= beam, "%s: n_best %d outside 1..beam (%d)", who, (int)n_best, (int)beam);
+  JS2T_CHECK(T_ < (int64_t(1) << 31) / CB_MAX_K, "%s: %lld frames exceed the node index", who, (long long)T_);
+  JS2T_CHECK(blank >= 0 && blank < V, "%s: blank %lld outside the vocabulary", who, (long long)blank);
+  JS2T_CHECK(dt == JS2T_F32 || dt == JS2T_BF16, "bad dtype %d", dt);
+  if (dt == JS2T_F32)
+    hipLaunchKernelGGL((ctc_beam_kernel<float, LM>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const float*)logits, lse,
+                       cand_id, cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand, (int)n_best,
+                       (int)blank, pad, row_offsets, fuse);
+  else
+    hipLaunchKernelGGL((ctc_beam_kernel<uint16_t, LM>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const uint16_t*)logits,
+                       lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand,
+                       (int)n_best, (int)blank, pad, row_offsets, fuse);
+  JS2T_LAUNCH_CHECK();
+  return JS2T_OK;
 }
 
 inline int64_t cb_nodes_per_utt(int64_t T, int64_t K) { return 1 + K * T; }
@@ -201,22 +315,40 @@ extern "C" int js2t_ctc_beam_search(const void* logits, int dt, const float* lse
                                     int64_t B, int64_t T_, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank,
                                     int64_t pad, const int32_t* row_offsets, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
-  JS2T_CHECK(logits && lse && cand_id && cand_lp && in_len && out_ids && out_len && out_score && workspace, "ctc_beam_search: null pointer");
-  JS2T_CHECK(B > 0 && T_ > 0 && V > 0 && V < 0x7fffffff, "ctc_beam_search: bad shape");
-  JS2T_CHECK(beam >= 1 && beam <= CB_MAX_K, "ctc_beam_search: beam %d outside 1..%d", (int)beam, CB_MAX_K);
-  JS2T_CHECK(n_cand >= 1 && n_cand <= CB_MAX_C, "ctc_beam_search: %d candidates outside 1..%d", (int)n_cand, CB_MAX_C);
-  JS2T_CHECK(n_best >= 1 && n_best <= beam, "ctc_beam_search: n_best %d outside 1..beam (%d)", (int)n_best, (int)beam);
-  JS2T_CHECK(T_ < (int64_t(1) << 31) / CB_MAX_K, "ctc_beam_search: %lld frames exceed the node index", (long long)T_);
-  JS2T_CHECK(blank >= 0 && blank < V, "ctc_beam_search: blank %lld outside the vocabulary", (long long)blank);
-  JS2T_CHECK(dt == JS2T_F32 || dt == JS2T_BF16, "bad dtype %d", dt);
-  if (dt == JS2T_F32)
-    hipLaunchKernelGGL(ctc_beam_kernel<float>, dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const float*)logits, lse, cand_id,
-                       cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand, (int)n_best, (int)blank,
-                       pad, row_offsets);
-  else
-    hipLaunchKernelGGL(ctc_beam_kernel<uint16_t>, dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const uint16_t*)logits, lse,
-                       cand_id, cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand, (int)n_best,
-                       (int)blank, pad, row_offsets);
-  JS2T_LAUNCH_CHECK();
-  return JS2T_OK;
+  return cb_launch<false>("ctc_beam_search", logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam,
+                          n_cand, n_best, blank, pad, row_offsets, CbFuse{}, stream);
+}
+
+extern "C" int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+                                       const int64_t* in_len, const float* uni, const void* table, int64_t capacity, int32_t max_probe,
+                                       int32_t lm_order, int64_t* out_ids, int32_t* out_len, float* out_score, float* out_ctc, float* out_lm,
+                                       void* workspace, int64_t B, int64_t T_, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best,
+                                       int64_t blank, int64_t pad, int64_t bos, int64_t eos, float lm_weight, float length_bonus,
+                                       const int32_t* row_offsets, js2t_stream stream) {
+  if (B == 0) return JS2T_OK;
+  const char* who = "ctc_beam_search_lm";
+  JS2T_CHECK(out_ctc && out_lm, "%s: null pointer (out_ctc / out_lm)", who);
+  JS2T_CHECK(V >= 2 && V <= 65535, "%s: V %lld outside 2..65535", who, (long long)V);
+  JS2T_CHECK(bos >= 0 && bos < V, "%s: bos %lld outside the vocabulary", who, (long long)bos);
+  JS2T_CHECK(eos >= 0 && eos < V, "%s: eos %lld outside the vocabulary", who, (long long)eos);
+  JS2T_CHECK(lm_order >= 1 && lm_order <= NGRAM_MAX_ORDER, "%s: order %d outside 1..%d", who, (int)lm_order, NGRAM_MAX_ORDER);
+  JS2T_CHECK(capacity >= 0 && (capacity & (capacity - 1)) == 0, "%s: capacity %lld is neither 0 nor a power of two", who, (long long)capacity);
+  JS2T_CHECK(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight %g / length_bonus %g not finite", who, (double)lm_weight,
+             (double)length_bonus);
+  if (lm_weight != 0.f) {  // a weight of exactly 0 leaves the model out: uni and table are not read and may be NULL
+    JS2T_CHECK(uni, "%s: null pointer (uni, with lm_weight %g)", who, (double)lm_weight);
+    if (lm_order > 1) {
+      JS2T_CHECK(table && capacity >= 1, "%s: order %d needs a table (capacity %lld)", who, (int)lm_order, (long long)capacity);
+      JS2T_CHECK(((uintptr_t)table & 15) == 0, "%s: table not 16-byte aligned", who);
+      JS2T_CHECK(max_probe >= 1 && (int64_t)max_probe <= capacity, "%s: max_probe %d outside 1..capacity (%lld)", who, (int)max_probe,
+                 (long long)capacity);
+    }
+  }
+  CbFuse fuse;
+  fuse.lm.uni = (const float2*)uni, fuse.lm.table = (const uint4*)table, fuse.lm.mask = capacity > 0 ? (uint64_t)capacity - 1 : 0;
+  fuse.lm.max_probe = max_probe, fuse.lm.order = lm_order, fuse.lm.V = (int)V;
+  fuse.bos = (int)bos, fuse.eos = (int)eos, fuse.lm_weight = lm_weight, fuse.length_bonus = length_bonus;
+  fuse.out_ctc = out_ctc, fuse.out_lm = out_lm;
+  return cb_launch<true>(who, logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam, n_cand, n_best,
+                         blank, pad, row_offsets, fuse, stream);
 }

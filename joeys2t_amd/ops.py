@@ -843,6 +843,53 @@ def ctc_beam_search(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: 
     return ids, n, score
 
 
+def ctc_beam_search_lm(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: int, blank: int, pad: int, lm, bos: int, eos: int,
+                       lm_weight: float, length_bonus: float, pack: "PackedRows" = None, workspace=None):
+    """CTC prefix beam search with the n-gram LM fused into the beam (js2t_ctc_beam_search_lm): ctc_beam_search's arguments; lm: a
+    joeys2t_amd.lm.NGramLM over the V ids of the logits on their device, or None when lm_weight is 0.  Every frame prunes by
+    ctc + lm_weight * lm + length_bonus * length; the final score adds the LM's EOS term.  Returns (ids i64 [B, n_best, T] pad-filled,
+    lengths i32 [B, n_best], scores f32 [B, n_best] = the final score, ctc f32 [B, n_best] = the CTC log-mass of the labelling,
+    lm f32 [B, n_best] = the LM's log-probability of the labels and of EOS, 0 without an LM), best first; -inf / 0 / pad in the slots
+    an utterance has no prefix for."""
+    _dev(logits3d, lse, cand_id, cand_lp, in_len, workspace)
+    B, T, V, roff = _ctc_geometry(logits3d, pack)
+    rows = logits3d.numel() // V
+    if cand_id.dim() != 2 or cand_id.shape[0] != rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
+            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
+        raise Js2tError(f"ctc_beam_search_lm: contiguous candidate tables i64 / f32 [{rows}, n_cand] expected, got "
+                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
+    if lse.numel() != rows or lse.dtype != torch.float32 or not logits3d.is_contiguous() or not lse.is_contiguous():
+        raise Js2tError(f"ctc_beam_search_lm: contiguous logits and f32 lse [{rows}] expected")
+    dev = logits3d.device
+    if lm is None:
+        if float(lm_weight) != 0.0:
+            raise Js2tError("ctc_beam_search_lm: without an lm, lm_weight 0 expected")
+        uni = table = None
+        capacity, max_probe, order_lm = 0, 1, 1
+    else:
+        if lm.uni_dev is None or lm.uni_dev.device != dev:
+            raise Js2tError(f"ctc_beam_search_lm: the lm is on {lm.device}, the logits on {dev}: lm.to(device) first")
+        if lm.V != V:
+            raise Js2tError(f"ctc_beam_search_lm: the lm is over {lm.V} ids, the logits over {V}")
+        uni, table = lm.uni_dev, (lm.table_dev if lm.capacity else None)
+        capacity, max_probe, order_lm = lm.capacity, lm.max_probe, lm.order
+    in_len = in_len.to(torch.int64).contiguous()
+    need = ctc_beam_workspace_bytes(B, T, beam)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"ctc_beam_search_lm: a contiguous workspace of {need} bytes expected")
+    nb = max(int(n_best), 0)
+    ids = torch.empty((B, nb, T), dtype=torch.int64, device=dev)
+    n = torch.empty((B, nb), dtype=torch.int32, device=dev)
+    score, ctc, lms = (torch.empty((B, nb), dtype=torch.float32, device=dev) for _ in range(3))
+    check(lib().js2t_ctc_beam_search_lm(_p(logits3d), dt_code(logits3d), _p(lse), _p(cand_id), _p(cand_lp), _p(in_len), _p(uni), _p(table),
+                                        capacity, max_probe, order_lm, _p(ids), _p(n), _p(score), _p(ctc), _p(lms), _p(workspace), B, T, V,
+                                        beam, cand_id.shape[1], n_best, blank, pad, int(bos), int(eos), float(lm_weight),
+                                        float(length_bonus), roff, _stream()), "js2t_ctc_beam_search_lm")
+    return ids, n, score, ctc, lms
+
+
 def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, out=None):
     """Attention rescoring of an n-best list (js2t_rescore): logits3d [R, Lp, V] f32 / bf16, the teacher-forced decoder output of
     R = B * N hypotheses (row l = the distribution after l labels; dense rows, any storage offset - a view is fine); ids i64

@@ -28,7 +28,7 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
             decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
-            length_bonus: float = 0.0):
+            length_bonus: float = 0.0, lm_fusion: str = "rescore"):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -44,14 +44,21 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     scores are the combined ones.  `ctc_weight` is read by this decoder only.
     lm / lm_weight / length_bonus (EXTENSION): an n-gram LM over the target vocabulary (joeys2t_amd.lm.NGramLM) and a bonus per label,
     handed to the two CTC decoders, which re-rank their n-best list with them on the device; the attention decoder has no place
-    for them and refuses them."""
+    for them and refuses them.  lm_fusion="search" (EXTENSION; default "rescore") applies them inside the CTC beam of either CTC
+    decoder instead (shallow fusion, `search.ctc_beam_search`); the attention decoder refuses it too."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
     if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
         raise ValueError("predict: lm / lm_weight / length_bonus re-rank the n-best list of decoder='ctc' or 'ctc-attention'; "
                          "decoder='attention' cannot apply them")
+    if lm_fusion not in ("rescore", "search"):
+        raise ValueError(f"predict: lm_fusion '{lm_fusion}' is neither 'rescore' nor 'search'")
+    if decoder == "attention" and lm_fusion != "rescore":
+        raise ValueError("predict: lm_fusion applies to the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
     lm_kw = {} if lm is None and float(lm_weight) == 0.0 and float(length_bonus) == 0.0 else \
         dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
+    if lm_fusion != "rescore":
+        lm_kw = dict(lm_kw, lm_fusion=lm_fusion)  # (without an lm or a bonus the decoder refuses it)
     ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}

@@ -506,8 +506,25 @@ def _ngram_rerank(model, ids, n, base, N, lm, lm_weight, length_bonus, dev, **kw
     return ops.ngram_rescore(ids, n, base, N, lm, model.bos_index, model.eos_index, lm_weight, length_bonus, V=len(model.trg_vocab), **kw)
 
 
+def _lm_fusion_arg(who, lm_fusion, rerank):
+    """is the LM fused into the beam ("search") instead of re-ranking its n-best list ("rescore", the default)?"""
+    if lm_fusion not in ("rescore", "search"):
+        raise ValueError(f"{who}: lm_fusion '{lm_fusion}' is neither 'rescore' nor 'search'")
+    if lm_fusion == "search" and not rerank:
+        raise ValueError(f"{who}: lm_fusion='search' without an lm or a length_bonus")
+    return lm_fusion == "search"
+
+
+def _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, beam_size, N, lm, lm_weight, length_bonus):
+    """ops.ctc_beam_search_lm over the model's vocabulary (blank = BOS), the lm moved to the device if need be"""
+    if lm is not None and lm.device != logits.device:
+        lm.to(logits.device)
+    return ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm, model.bos_index,
+                                  model.eos_index, lm_weight, length_bonus)
+
+
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
-                    length_bonus: float = 0.0, n_rescore: int = None):
+                    length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore"):
     """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
     `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
     `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
@@ -517,11 +534,29 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus`, the `n_rescore` (default:
     beam_size) best prefixes are searched for, re-ranked on the device by ctc + lm_weight * lm + length_bonus * n, lm = the LM's
     log-probability of the labels and of EOS behind them (js2t_ngram_rescore), and the n_best first are returned with that score;
-    there is no host read between the encoder and the final copy.  Without either the search runs as it always did."""
+    there is no host read between the encoder and the final copy.  Without either the search runs as it always did.
+    lm_fusion="search" applies the LM and the bonus INSIDE the beam instead (shallow fusion, js2t_ctc_beam_search_lm): every frame
+    prunes by ctc + lm_weight * lm + length_bonus * n, so a labelling the LM prefers survives where the CTC score alone would have
+    dropped it; the returned scores are the kernel's final scores (EOS term included).  There is no list to re-rank: n_rescore is
+    refused."""
     from joeys2t_amd.alignment import _ctc_frames
     rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
+    fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
     if not 1 <= n_best <= beam_size:
         raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
+    if fused:
+        if n_rescore is not None:
+            raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
+        with torch.no_grad():
+            ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
+            B, T, V = ctc_out.shape
+            logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
+            cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+            ids, n, score, _, _ = _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, int(beam_size), int(n_best), lm, lm_weight,
+                                                  length_bonus)
+        n = n.cpu().numpy().astype(np.int64).reshape(B * n_best)
+        L = max(int(n.max()) if n.size else 0, 1)
+        return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
     if rerank:
         n_rescore = int(beam_size if n_rescore is None else n_rescore)
         if not n_best <= n_rescore <= beam_size:
@@ -561,7 +596,7 @@ def _ctc_beam_search_lm(model, batch, beam_size, n_best, candidates, lm, lm_weig
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
                           n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
-                          length_bonus: float = 0.0):
+                          length_bonus: float = 0.0, lm_fusion: str = "rescore"):
     """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
     of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
     over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
@@ -576,9 +611,13 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     list of f32 arrays of n + 1 values, the last one EOS's) and "ctc_rank" i64 [B * n_best] (the slot of the row in the CTC n-best).
     With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus` the final score is
     ctc_weight * ctc + (1 - ctc_weight) * attention + lm_weight * lm + length_bonus * n: js2t_rescore's combined score is the base
-    score of js2t_ngram_rescore, whose ranking decides; the parts gain "lm" f32 [B * n_best] and "lm_token_log_probs"."""
+    score of js2t_ngram_rescore, whose ranking decides; the parts gain "lm" f32 [B * n_best] and "lm_token_log_probs".
+    lm_fusion="search": the first pass is the LM-fused beam search (js2t_ctc_beam_search_lm with n_best = n_rescore), so the list
+    that is re-scored already holds the labellings the LM prefers; its pure CTC score (out_ctc) is js2t_rescore's CTC score, the
+    rest is unchanged and "ctc_rank" is the slot in the fused list."""
     from joeys2t_amd.alignment import _ctc_frames
     rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
+    fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
     n_rescore = beam_size if n_rescore is None else n_rescore
     beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
     if not 1 <= n_best <= n_rescore <= beam_size <= 32:
@@ -594,7 +633,10 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         dev = ctc_out.device
         logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
         cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
+        if fused:
+            ids, n, _, ctc, _ = _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, beam_size, N, lm, lm_weight, length_bonus)
+        else:
+            ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
         Lp = int(n.max().item()) + 1 if n.numel() else 1  # the one host read: it sizes the decoder pass
         ids2 = ids.view(B * N, T)
         trg_input = torch.cat([torch.full((B * N, 1), model.bos_index, dtype=torch.int64, device=dev), ids2[:, :Lp - 1]], dim=1).contiguous()
