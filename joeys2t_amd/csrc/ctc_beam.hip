@@ -21,13 +21,17 @@
 // barrier and no other global traffic per frame.  After the last frame one wave adds the EOS term,
 // ranks the beam again by counting and the back-trace runs in that order.  With LM = false none of it is compiled: that form is
 // what js2t_ctc_beam_search launches.
+//
+// The limit on the beam, the fusion rule, the final ranking and the hash's finaliser are nbest.hpp's, shared with rescore.hip and
+// ngram.hip, so the list this kernel writes is ranked as they rank it; the checks of the LM arguments are ngram.hpp's ngram_args.
 #include "common.hpp"
+#include "nbest.hpp"
 #include "ngram.hpp"
 
 namespace {
 
 constexpr int CB_THREADS = 256;
-constexpr int CB_MAX_K = 32;
+constexpr int CB_MAX_K = NBEST_MAX_N;                       // a beam is an n-best list: one lane per slot in the final ranking
 constexpr int CB_MAX_C = 8;                                 // the limit of js2t_beam_pick
 constexpr int CB_MAX_E = CB_MAX_K + CB_MAX_K * CB_MAX_C;    // proposals per frame: 288 (a multiple of 4)
 constexpr int CB_CHUNK = 64;                                // frames whose candidate rows are staged at a time: 4.25 KB of LDS
@@ -36,12 +40,7 @@ constexpr uint64_t CB_ROOT_HASH = 0x9E3779B97F4A7C15ull;
 
 // h(y + c) = fmix(h(y) ^ (c + 1)), fmix = the finaliser of splitmix64 (a bijection of 64-bit words; h ^ (c + 1) is injective in c,
 // so the children of one prefix never collide)
-__device__ __forceinline__ uint64_t cb_mix(uint64_t h, int c) {
-  uint64_t z = h ^ (uint64_t)(uint32_t)(c + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+__device__ __forceinline__ uint64_t cb_mix(uint64_t h, int c) { return nbest_fmix(h ^ (uint64_t)(uint32_t)(c + 1)); }
 
 // log(exp a + exp b) on the hardware's exp / log (beam.hip ctc_lae_fast: absolute error ~1e-7 per call); lae(-inf, x) = x, never NaN
 __device__ __forceinline__ float cb_lae(float a, float b) {
@@ -69,16 +68,6 @@ struct CbFuse {  // what the LM form takes besides the search's own arguments
   float lm_weight, length_bonus;
   float *out_ctc, *out_lm;
 };
-
-// ctc + lm_weight * lm + length_bonus * len, each product rounded to f32 and added in that order, a term of weight 0 left out
-// (js2t_ngram_rescore's rule)
-__device__ __forceinline__ float cb_fuse(float ctc, float lm, int len, float lm_weight, float length_bonus) {
-#pragma clang fp contract(off)
-  float s = ctc;
-  if (lm_weight != 0.f) s += lm_weight * lm;
-  if (length_bonus != 0.f) s += length_bonus * (float)len;
-  return s;
-}
 
 // log p(w | (bos, y)) for the prefix y in slot i of the beam
 template <bool LM>
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
               if (g.len[i] + 1 == len && g.hash[i] == ph) npnb = cb_lae(npnb, (g.last[i] == last ? g.pb[i] : g.tot[i]) + lp_rep);
           }
           key = cb_lae(npb, npnb);
-          if constexpr (LM) elm = g.lm[e], key = cb_fuse(key, elm, len, fuse.lm_weight, fuse.length_bonus);
+          if constexpr (LM) elm = g.lm[e], key = nbest_fuse(key, elm, len, fuse.lm_weight, fuse.length_bonus);
         } else if (e >= K && e < nlive) {
           const int i = (e - K) / C, s = (e - K) - i * C;
           const int c = s_cid[tt][s];
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
             if (ok) {
               npnb = base + s_clp[tt][s];
               key = npnb;
-              if constexpr (LM) key = cb_fuse(key, elm, len1, fuse.lm_weight, fuse.length_bonus);
+              if constexpr (LM) key = nbest_fuse(key, elm, len1, fuse.lm_weight, fuse.length_bonus);
             }
           }
         }
@@ -229,21 +218,16 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
   // the nodes (workgroup scope), visible
   const CbBeam<LM>& g = beam[cur];
   if constexpr (LM) {
-    // the EOS term and the final score, lanes < nbeam of the first wave; ranked again by counting (equal finals keep the beam's
-    // order, a NaN ranks as -inf); the back-trace below runs in that order
+    // the EOS term and the final score, lanes < nbeam of the first wave; ranked again by nbest.hpp's rule (equal finals keep the
+    // beam's order, a NaN ranks as -inf); the back-trace below runs in that order
     if (tid < 64) {  // (wave-uniform)
       const bool have = tid < nbeam;
       float lmf = 0.f, fin = -INFINITY;
       if (have) {
         if (fuse.lm_weight != 0.f) lmf = g.lm[tid] + cb_token_logp(fuse, g, tid, fuse.eos);
-        fin = cb_fuse(g.tot[tid], lmf, g.len[tid], fuse.lm_weight, fuse.length_bonus);
+        fin = nbest_fuse(g.tot[tid], lmf, g.len[tid], fuse.lm_weight, fuse.length_bonus);
       }
-      const float key = fin == fin ? fin : -INFINITY;
-      int rank = 0;
-      for (int j = 0; j < nbeam; ++j) {  // (block-uniform bounds)
-        const float kj = __shfl(key, j, 64);
-        rank += (kj > key || (kj == key && j < tid)) ? 1 : 0;
-      }
+      const int rank = nbest_rank(fin, tid, nbeam);  // (block-uniform nbeam)
       if (have) s_ord[rank] = tid, s_fin[tid] = fin, s_lmf[tid] = lmf;
     }
     __syncthreads();
@@ -328,25 +312,8 @@ extern "C" int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* 
   if (B == 0) return JS2T_OK;
   const char* who = "ctc_beam_search_lm";
   JS2T_CHECK(out_ctc && out_lm, "%s: null pointer (out_ctc / out_lm)", who);
-  JS2T_CHECK(V >= 2 && V <= 65535, "%s: V %lld outside 2..65535", who, (long long)V);
-  JS2T_CHECK(bos >= 0 && bos < V, "%s: bos %lld outside the vocabulary", who, (long long)bos);
-  JS2T_CHECK(eos >= 0 && eos < V, "%s: eos %lld outside the vocabulary", who, (long long)eos);
-  JS2T_CHECK(lm_order >= 1 && lm_order <= NGRAM_MAX_ORDER, "%s: order %d outside 1..%d", who, (int)lm_order, NGRAM_MAX_ORDER);
-  JS2T_CHECK(capacity >= 0 && (capacity & (capacity - 1)) == 0, "%s: capacity %lld is neither 0 nor a power of two", who, (long long)capacity);
-  JS2T_CHECK(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight %g / length_bonus %g not finite", who, (double)lm_weight,
-             (double)length_bonus);
-  if (lm_weight != 0.f) {  // a weight of exactly 0 leaves the model out: uni and table are not read and may be NULL
-    JS2T_CHECK(uni, "%s: null pointer (uni, with lm_weight %g)", who, (double)lm_weight);
-    if (lm_order > 1) {
-      JS2T_CHECK(table && capacity >= 1, "%s: order %d needs a table (capacity %lld)", who, (int)lm_order, (long long)capacity);
-      JS2T_CHECK(((uintptr_t)table & 15) == 0, "%s: table not 16-byte aligned", who);
-      JS2T_CHECK(max_probe >= 1 && (int64_t)max_probe <= capacity, "%s: max_probe %d outside 1..capacity (%lld)", who, (int)max_probe,
-                 (long long)capacity);
-    }
-  }
   CbFuse fuse;
-  fuse.lm.uni = (const float2*)uni, fuse.lm.table = (const uint4*)table, fuse.lm.mask = capacity > 0 ? (uint64_t)capacity - 1 : 0;
-  fuse.lm.max_probe = max_probe, fuse.lm.order = lm_order, fuse.lm.V = (int)V;
+  if (const int rc = ngram_args(who, uni, table, capacity, max_probe, lm_order, V, bos, eos, lm_weight, length_bonus, &fuse.lm)) return rc;
   fuse.bos = (int)bos, fuse.eos = (int)eos, fuse.lm_weight = lm_weight, fuse.length_bonus = length_bonus;
   fuse.out_ctc = out_ctc, fuse.out_lm = out_lm;
   return cb_launch<true>(who, logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam, n_cand, n_best,

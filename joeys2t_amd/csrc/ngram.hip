@@ -8,31 +8,29 @@
 //      has up to 64 x 7 loads in flight and the block no barrier.  The lane sums its own positions in ascending order and the wave
 //      adds the 64 partial sums in the fixed butterfly of wave_sum: the order depends on n[r] alone.  The same wave combines.
 //      A dead slot, and every slot when lm_weight is 0, stores its zeros and reads neither ids nor the model.
-//   2. ngram_rank_kernel: one wave per utterance; lane k < N ranks its slot by counting over shuffled keys (the rule of
-//      rescore.hip's rank kernel, restated here so that file stays as it is).
+//   2. ngram_rank_kernel: one wave per utterance; lane k < N ranks its slot by nbest.hpp's rule.
+//
+// The dead-slot rule, the fusion rule, the ranking and the limit on N are nbest.hpp's, shared with rescore.hip and ctc_beam.hip; the
+// checks of the LM arguments are ngram.hpp's ngram_args, shared with ctc_beam.hip.
 //
 // No atomics, no allocation, no workspace, no host synchronisation: bit-reproducible, capturable.
 #include "common.hpp"
+#include "nbest.hpp"
 #include "ngram.hpp"
 
 namespace {
-
-constexpr int NG_MAX_N = 32;
-
-__device__ __forceinline__ bool ng_dead(float base, int n, int64_t Lp) { return base == -INFINITY || n < 0 || (int64_t)n > Lp - 1; }
 
 __global__ __launch_bounds__(256) void ngram_score_kernel(const int64_t* __restrict__ ids, int64_t ids_stride, const int32_t* __restrict__ n,
                                                           const float* __restrict__ base_score, const ngram_view lm,
                                                           float* __restrict__ lm_tok, float* __restrict__ lm_score,
                                                           float* __restrict__ score, int64_t R, int64_t Lp, int64_t bos, int64_t eos,
                                                           float lm_weight, float length_bonus) {
-#pragma clang fp contract(off)  // score = base + (w * lm) + (b * n), each product rounded: what the header states
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;  // (wave-uniform; no barriers below)
   const int nr = n[r];
   const float bs = base_score[r];
-  const bool dead = ng_dead(bs, nr, Lp);
+  const bool dead = nbest_dead(bs, nr, Lp);
   float sum = 0.f;
   if (dead || lm_weight == 0.f) {  // (wave-uniform) nothing of the ids or of the model is read
     if (lm_tok)
@@ -56,11 +54,7 @@ __global__ __launch_bounds__(256) void ngram_score_kernel(const int64_t* __restr
   }
   if (lane == 0) {
     float sc = -INFINITY;
-    if (!dead) {
-      sc = bs;  // a term of weight 0 is left out, not multiplied
-      if (lm_weight != 0.f) sc += lm_weight * sum;
-      if (length_bonus != 0.f) sc += length_bonus * (float)nr;
-    }
+    if (!dead) sc = nbest_fuse(bs, sum, nr, lm_weight, length_bonus);
     lm_score[r] = dead ? -INFINITY : sum;
     score[r] = sc;
   }
@@ -69,12 +63,7 @@ __global__ __launch_bounds__(256) void ngram_score_kernel(const int64_t* __restr
 __global__ __launch_bounds__(64) void ngram_rank_kernel(const float* __restrict__ score, int32_t* __restrict__ order, int N) {
   const int k = threadIdx.x;
   const float sc = k < N ? score[(int64_t)blockIdx.x * N + k] : -INFINITY;
-  const float key = sc == sc ? sc : -INFINITY;  // a NaN ranks as -inf: the permutation does not depend on the data
-  int rank = 0;
-  for (int j = 0; j < N; ++j) {  // (wave-uniform bounds)
-    const float kj = __shfl(key, j, 64);
-    rank += (kj > key || (kj == key && j < k)) ? 1 : 0;
-  }
+  const int rank = nbest_rank(sc, k, N);
   if (k < N) order[(int64_t)blockIdx.x * N + rank] = k;
 }
 
@@ -86,31 +75,13 @@ extern "C" int js2t_ngram_rescore(const int64_t* ids, int64_t ids_stride, const 
                                   int64_t eos, float lm_weight, float length_bonus, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(ids && n && base_score && lm_score && score && order, "ngram_rescore: null pointer");
-  JS2T_CHECK(N >= 1 && N <= NG_MAX_N, "ngram_rescore: N %d outside 1..%d", (int)N, NG_MAX_N);
+  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "ngram_rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
   JS2T_CHECK(Lp >= 1, "ngram_rescore: Lp %lld below 1", (long long)Lp);
-  JS2T_CHECK(V >= 2 && V <= 65535, "ngram_rescore: V %lld outside 2..65535", (long long)V);
-  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NG_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
-             "ngram_rescore: bad shape (B %lld, Lp %lld)", (long long)B, (long long)Lp);
-  JS2T_CHECK(bos >= 0 && bos < V, "ngram_rescore: bos %lld outside the vocabulary", (long long)bos);
-  JS2T_CHECK(eos >= 0 && eos < V, "ngram_rescore: eos %lld outside the vocabulary", (long long)eos);
-  JS2T_CHECK(ids_stride >= Lp - 1, "ngram_rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
-  JS2T_CHECK(lm_order >= 1 && lm_order <= NGRAM_MAX_ORDER, "ngram_rescore: order %d outside 1..%d", (int)lm_order, NGRAM_MAX_ORDER);
-  JS2T_CHECK(capacity >= 0 && (capacity & (capacity - 1)) == 0, "ngram_rescore: capacity %lld is neither 0 nor a power of two",
-             (long long)capacity);
-  JS2T_CHECK(isfinite(lm_weight) && isfinite(length_bonus), "ngram_rescore: lm_weight %g / length_bonus %g not finite",
-             (double)lm_weight, (double)length_bonus);
-  if (lm_weight != 0.f) {  // a weight of exactly 0 leaves the model out: uni and table are not read and may be NULL
-    JS2T_CHECK(uni, "ngram_rescore: null pointer (uni, with lm_weight %g)", (double)lm_weight);
-    if (lm_order > 1) {
-      JS2T_CHECK(table && capacity >= 1, "ngram_rescore: order %d needs a table (capacity %lld)", (int)lm_order, (long long)capacity);
-      JS2T_CHECK(((uintptr_t)table & 15) == 0, "ngram_rescore: table not 16-byte aligned");
-      JS2T_CHECK(max_probe >= 1 && (int64_t)max_probe <= capacity, "ngram_rescore: max_probe %d outside 1..capacity (%lld)", (int)max_probe,
-                 (long long)capacity);
-    }
-  }
   ngram_view lm;
-  lm.uni = (const float2*)uni, lm.table = (const uint4*)table, lm.mask = capacity > 0 ? (uint64_t)capacity - 1 : 0;
-  lm.max_probe = max_probe, lm.order = lm_order, lm.V = (int)V;
+  if (const int rc = ngram_args("ngram_rescore", uni, table, capacity, max_probe, lm_order, V, bos, eos, lm_weight, length_bonus, &lm)) return rc;
+  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
+             "ngram_rescore: bad shape (B %lld, Lp %lld)", (long long)B, (long long)Lp);
+  JS2T_CHECK(ids_stride >= Lp - 1, "ngram_rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
   const int64_t R = B * N;
   hipLaunchKernelGGL(ngram_score_kernel, dim3((unsigned)cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, ids, ids_stride, n, base_score, lm,
                      lm_tok, lm_score, score, R, Lp, bos, eos, lm_weight, length_bonus);

@@ -1,10 +1,12 @@
 // Back-off n-gram language model on the device: the table view, the key packing and the log-probability of one token given its
 // history (EXTENSION; the reference has no language model).  The layout and the rules are stated in the header at
-// js2t_ngram_rescore; this file is what a kernel includes to apply them (ngram.hip does; an in-search fusion can).
+// js2t_ngram_rescore; this file is what a kernel includes to apply them (ngram.hip and ctc_beam.hip do), and its ngram_args is what
+// their entry points check the LM arguments with.
 //
 //   uni   f32 [V, 2]: (logp, backoff) of every id, dense.
 //   table `capacity` (a power of two) entries of 16 bytes {u64 key, f32 logp, f32 backoff}: the 2-grams .. order-grams, open
-//         addressing with linear probing and wrap-around, home slot fmix(key) & (capacity - 1), fmix = the splitmix64 finaliser.
+//         addressing with linear probing and wrap-around, home slot fmix(key) & (capacity - 1), fmix = the splitmix64 finaliser
+//         (nbest.hpp's nbest_fmix).
 //   key   of (w1 .. wk): field j (0 = newest = wk) = id + 1 in bits 16j .. 16j+15; 0 = an empty slot.  The key IS the n-gram:
 //         a match is exact.
 //
@@ -12,9 +14,8 @@
 // computable from the ids alone) and the two unigram loads before it looks at any of them: one memory latency for the position,
 // not one per back-off level.  Only a first probe that meets another key walks on, at most max_probe slots in all.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <math.h>
+#include "common.hpp"
+#include "nbest.hpp"
 
 constexpr int NGRAM_MAX_ORDER = 4;
 constexpr int NGRAM_MAX_CTX = NGRAM_MAX_ORDER - 1;
@@ -28,10 +29,29 @@ struct ngram_view {
   int V;               // 2 .. 65535
 };
 
-__host__ __device__ __forceinline__ uint64_t ngram_fmix(uint64_t z) {
-  z ^= z >> 30, z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27, z *= 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
+// (host) the LM arguments of the entry point `who` - js2t_ngram_rescore's, which js2t_ctc_beam_search_lm takes too: checked in
+// this order with these messages, and the view filled
+inline int ngram_args(const char* who, const float* uni, const void* table, int64_t capacity, int32_t max_probe, int32_t lm_order, int64_t V,
+                      int64_t bos, int64_t eos, float lm_weight, float length_bonus, ngram_view* lm) {
+  JS2T_CHECK(V >= 2 && V <= 65535, "%s: V %lld outside 2..65535", who, (long long)V);
+  JS2T_CHECK(bos >= 0 && bos < V, "%s: bos %lld outside the vocabulary", who, (long long)bos);
+  JS2T_CHECK(eos >= 0 && eos < V, "%s: eos %lld outside the vocabulary", who, (long long)eos);
+  JS2T_CHECK(lm_order >= 1 && lm_order <= NGRAM_MAX_ORDER, "%s: order %d outside 1..%d", who, (int)lm_order, NGRAM_MAX_ORDER);
+  JS2T_CHECK(capacity >= 0 && (capacity & (capacity - 1)) == 0, "%s: capacity %lld is neither 0 nor a power of two", who, (long long)capacity);
+  JS2T_CHECK(isfinite(lm_weight) && isfinite(length_bonus), "%s: lm_weight %g / length_bonus %g not finite", who, (double)lm_weight,
+             (double)length_bonus);
+  if (lm_weight != 0.f) {  // a weight of exactly 0 leaves the model out: uni and table are not read and may be NULL
+    JS2T_CHECK(uni, "%s: null pointer (uni, with lm_weight %g)", who, (double)lm_weight);
+    if (lm_order > 1) {
+      JS2T_CHECK(table && capacity >= 1, "%s: order %d needs a table (capacity %lld)", who, (int)lm_order, (long long)capacity);
+      JS2T_CHECK(((uintptr_t)table & 15) == 0, "%s: table not 16-byte aligned", who);
+      JS2T_CHECK(max_probe >= 1 && (int64_t)max_probe <= capacity, "%s: max_probe %d outside 1..capacity (%lld)", who, (int)max_probe,
+                 (long long)capacity);
+    }
+  }
+  lm->uni = (const float2*)uni, lm->table = (const uint4*)table, lm->mask = capacity > 0 ? (uint64_t)capacity - 1 : 0;
+  lm->max_probe = max_probe, lm->order = lm_order, lm->V = (int)V;
+  return JS2T_OK;
 }
 
 __device__ __forceinline__ uint64_t ngram_entry_key(const uint4 e) { return (uint64_t)e.x | ((uint64_t)e.y << 32); }
@@ -42,7 +62,7 @@ struct ngram_hit {
 };
 
 // slot of a key's first probe (a key of 0, "no such level", probes slot 0: a valid address whose value is not used)
-__device__ __forceinline__ uint64_t ngram_home(const ngram_view& lm, uint64_t key) { return key ? ngram_fmix(key) & lm.mask : 0; }
+__device__ __forceinline__ uint64_t ngram_home(const ngram_view& lm, uint64_t key) { return key ? nbest_fmix(key) & lm.mask : 0; }
 
 // the rest of a lookup whose first probe `e` (slot `home`) has been loaded; only a probe that met another key walks on
 __device__ __forceinline__ ngram_hit ngram_resolve(const ngram_view& lm, uint64_t key, uint64_t home, uint4 e) {

@@ -11,16 +11,15 @@
 //      chunks element by element, and so does the tail chunk of every row.  Both forms feed the same arithmetic in the same order:
 //      the bits do not depend on the alignment.
 //   2. rescore_rank_kernel: one wave per utterance; lane k < N sums its slot's token log-probabilities in ascending position, combines
-//      and ranks by counting over shuffled keys.
+//      and ranks by nbest.hpp's rule.
+//
+// The dead-slot rule, the ranking and the limit on N are nbest.hpp's, shared with ngram.hip and ctc_beam.hip.
 //
 // No atomics, no allocation, no workspace, no host synchronisation: bit-reproducible, capturable.
 #include "common.hpp"
+#include "nbest.hpp"
 
 namespace {
-
-constexpr int RS_MAX_N = 32;
-
-__device__ __forceinline__ bool rs_dead(float ctc, int n, int64_t Lp) { return ctc == -INFINITY || n < 0 || (int64_t)n > Lp - 1; }
 
 template <typename T> struct rs_chunk;  // E elements = 16 bytes
 template <> struct rs_chunk<float> {
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void rescore_tok_kernel(const T* __restrict__ 
   if (row >= rows) return;  // (no barriers below)
   const int64_t r = row / Lp, l = row - r * Lp;
   const int nr = n[r];
-  if (rs_dead(ctc_score[r], nr, Lp) || l > (int64_t)nr) {  // (wave-uniform) nothing of this row is read
+  if (nbest_dead(ctc_score[r], nr, Lp) || l > (int64_t)nr) {  // (wave-uniform) nothing of this row is read
     if (lane == 0) tok_lp[row] = 0.f;
     return;
   }
@@ -131,7 +130,7 @@ __global__ __launch_bounds__(64) void rescore_rank_kernel(const int32_t* __restr
     const float cs = ctc_score[r];
     const int nr = n[r];
     float att = -INFINITY;
-    if (!rs_dead(cs, nr, Lp)) {
+    if (!nbest_dead(cs, nr, Lp)) {
       att = 0.f;
       const float* tp = tok_lp + r * Lp;
       for (int l0 = 0; l0 <= nr; l0 += 8) {  // eight independent loads at a time; the additions in ascending l, one fixed order
@@ -147,12 +146,7 @@ __global__ __launch_bounds__(64) void rescore_rank_kernel(const int32_t* __restr
     att_score[r] = att;
     score[r] = sc;
   }
-  const float key = sc == sc ? sc : -INFINITY;  // a NaN ranks as -inf: the permutation does not depend on the data
-  int rank = 0;
-  for (int j = 0; j < N; ++j) {  // (wave-uniform bounds)
-    const float kj = __shfl(key, j, 64);
-    rank += (kj > key || (kj == key && j < k)) ? 1 : 0;
-  }
+  const int rank = nbest_rank(sc, k, N);  // (every lane: a lane >= N holds -inf)
   if (k < N) order[(int64_t)blockIdx.x * N + rank] = k;
 }
 
@@ -163,10 +157,10 @@ extern "C" int js2t_rescore(const void* logits, int dt, const int64_t* ids, int6
                             int64_t eos, float ctc_weight, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(logits && ids && n && ctc_score && tok_lp && att_score && score && order, "rescore: null pointer");
-  JS2T_CHECK(N >= 1 && N <= RS_MAX_N, "rescore: N %d outside 1..%d", (int)N, RS_MAX_N);
+  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
   JS2T_CHECK(Lp >= 1, "rescore: Lp %lld below 1", (long long)Lp);
   JS2T_CHECK(V >= 2 && V < 0x7fffffff, "rescore: V %lld outside 2..2^31-2", (long long)V);
-  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / RS_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
+  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
              "rescore: bad shape (B %lld, Lp %lld)", (long long)B, (long long)Lp);
   JS2T_CHECK(eos >= 0 && eos < V, "rescore: eos %lld outside the vocabulary", (long long)eos);
   JS2T_CHECK(ctc_weight >= 0.f && ctc_weight <= 1.f, "rescore: ctc_weight %g outside [0, 1]", (double)ctc_weight);  // (NaN fails too)

@@ -810,6 +810,48 @@ def ctc_beam_candidates(logits2d: torch.Tensor, n_cand: int, blank: int):
     return cand_id, cand_lp, lse
 
 
+def _beam_args(who, logits3d, lse, cand_id, cand_lp, in_len, beam, n_best, pack, workspace):
+    """What the two beam searches share in front of the library call: the checks of the candidate tables, the logits and lse, the
+    lengths as i64, the workspace (the caller's, checked, or a fresh one) and the three outputs both write.  Returns (B, T, V, row
+    offsets pointer, in_len, workspace, ids, n, score); `who` names the caller in the errors."""
+    _dev(logits3d, lse, cand_id, cand_lp, in_len, workspace)
+    B, T, V, roff = _ctc_geometry(logits3d, pack)
+    rows = logits3d.numel() // V
+    if cand_id.dim() != 2 or cand_id.shape[0] != rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
+            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
+        raise Js2tError(f"{who}: contiguous candidate tables i64 / f32 [{rows}, n_cand] expected, got "
+                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
+    if lse.numel() != rows or lse.dtype != torch.float32 or not logits3d.is_contiguous() or not lse.is_contiguous():
+        raise Js2tError(f"{who}: contiguous logits and f32 lse [{rows}] expected")
+    dev = logits3d.device
+    in_len = in_len.to(torch.int64).contiguous()
+    need = ctc_beam_workspace_bytes(B, T, beam)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"{who}: a contiguous workspace of {need} bytes expected")
+    nb = max(int(n_best), 0)
+    ids = torch.empty((B, nb, T), dtype=torch.int64, device=dev)
+    n = torch.empty((B, nb), dtype=torch.int32, device=dev)
+    score = torch.empty((B, nb), dtype=torch.float32, device=dev)
+    return B, T, V, roff, in_len, workspace, ids, n, score
+
+
+def _lm_args(who, lm, lm_weight, dev, on, V, own_V=False):
+    """The LM arguments of js2t_ngram_rescore and js2t_ctc_beam_search_lm from an NGramLM, or from None, which stands for lm_weight 0
+    over V ids: (uni, table, capacity, max_probe, order, V).  In the errors `who` names the caller and `on` what it holds on `dev`;
+    own_V: V is an argument of the caller's own (it may be None next to an lm), not the logits' width."""
+    if lm is None:
+        if float(lm_weight) != 0.0 or V is None:
+            raise Js2tError(f"{who}: without an lm, lm_weight 0{' and V' if own_V else ''} expected")
+        return None, None, 0, 1, 1, V
+    if lm.uni_dev is None or lm.uni_dev.device != dev:
+        raise Js2tError(f"{who}: the lm is on {lm.device}, the {on} on {dev}: lm.to(device) first")
+    if V is not None and int(V) != lm.V:
+        raise Js2tError(f"{who}: the lm is over {lm.V} ids, " + (f"V = {V}" if own_V else f"the {on} over {V}"))
+    return lm.uni_dev, (lm.table_dev if lm.capacity else None), lm.capacity, lm.max_probe, lm.order, lm.V
+
+
 def ctc_beam_search(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: int, blank: int, pad: int, pack: "PackedRows" = None,
                     workspace=None):
     """CTC prefix beam search (js2t_ctc_beam_search): logits / lse / in_len / pack as for ctc_alpha; cand_id i64 / cand_lp f32
@@ -817,26 +859,8 @@ def ctc_beam_search(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: 
     (ids i64 [B, n_best, T] pad-filled, lengths i32 [B, n_best], scores f32 [B, n_best], best first; -inf / 0 / pad in the slots an
     utterance has no prefix for).  workspace: a device buffer of >= ctc_beam_workspace_bytes(B, T, beam) bytes to use instead of a
     fresh one (contents are ignored)."""
-    _dev(logits3d, lse, cand_id, cand_lp, in_len, workspace)
-    B, T, V, roff = _ctc_geometry(logits3d, pack)
-    rows = logits3d.numel() // V
-    if cand_id.dim() != 2 or cand_id.shape[0] != rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
-            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
-        raise Js2tError(f"ctc_beam_search: contiguous candidate tables i64 / f32 [{rows}, n_cand] expected, got "
-                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
-    if lse.numel() != rows or lse.dtype != torch.float32 or not logits3d.is_contiguous() or not lse.is_contiguous():
-        raise Js2tError(f"ctc_beam_search: contiguous logits and f32 lse [{rows}] expected")
-    dev = logits3d.device
-    in_len = in_len.to(torch.int64).contiguous()
-    need = ctc_beam_workspace_bytes(B, T, beam)
-    if workspace is None:
-        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
-    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
-        raise Js2tError(f"ctc_beam_search: a contiguous workspace of {need} bytes expected")
-    nb = max(int(n_best), 0)
-    ids = torch.empty((B, nb, T), dtype=torch.int64, device=dev)
-    n = torch.empty((B, nb), dtype=torch.int32, device=dev)
-    score = torch.empty((B, nb), dtype=torch.float32, device=dev)
+    B, T, V, roff, in_len, workspace, ids, n, score = _beam_args("ctc_beam_search", logits3d, lse, cand_id, cand_lp, in_len, beam, n_best, pack,
+                                                                 workspace)
     check(lib().js2t_ctc_beam_search(_p(logits3d), dt_code(logits3d), _p(lse), _p(cand_id), _p(cand_lp), _p(in_len), _p(ids), _p(n),
                                      _p(score), _p(workspace), B, T, V, beam, cand_id.shape[1], n_best, blank, pad, roff, _stream()),
           "js2t_ctc_beam_search")
@@ -851,43 +875,49 @@ def ctc_beam_search_lm(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_bes
     lengths i32 [B, n_best], scores f32 [B, n_best] = the final score, ctc f32 [B, n_best] = the CTC log-mass of the labelling,
     lm f32 [B, n_best] = the LM's log-probability of the labels and of EOS, 0 without an LM), best first; -inf / 0 / pad in the slots
     an utterance has no prefix for."""
-    _dev(logits3d, lse, cand_id, cand_lp, in_len, workspace)
-    B, T, V, roff = _ctc_geometry(logits3d, pack)
-    rows = logits3d.numel() // V
-    if cand_id.dim() != 2 or cand_id.shape[0] != rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
-            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
-        raise Js2tError(f"ctc_beam_search_lm: contiguous candidate tables i64 / f32 [{rows}, n_cand] expected, got "
-                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
-    if lse.numel() != rows or lse.dtype != torch.float32 or not logits3d.is_contiguous() or not lse.is_contiguous():
-        raise Js2tError(f"ctc_beam_search_lm: contiguous logits and f32 lse [{rows}] expected")
-    dev = logits3d.device
-    if lm is None:
-        if float(lm_weight) != 0.0:
-            raise Js2tError("ctc_beam_search_lm: without an lm, lm_weight 0 expected")
-        uni = table = None
-        capacity, max_probe, order_lm = 0, 1, 1
-    else:
-        if lm.uni_dev is None or lm.uni_dev.device != dev:
-            raise Js2tError(f"ctc_beam_search_lm: the lm is on {lm.device}, the logits on {dev}: lm.to(device) first")
-        if lm.V != V:
-            raise Js2tError(f"ctc_beam_search_lm: the lm is over {lm.V} ids, the logits over {V}")
-        uni, table = lm.uni_dev, (lm.table_dev if lm.capacity else None)
-        capacity, max_probe, order_lm = lm.capacity, lm.max_probe, lm.order
-    in_len = in_len.to(torch.int64).contiguous()
-    need = ctc_beam_workspace_bytes(B, T, beam)
-    if workspace is None:
-        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
-    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
-        raise Js2tError(f"ctc_beam_search_lm: a contiguous workspace of {need} bytes expected")
-    nb = max(int(n_best), 0)
-    ids = torch.empty((B, nb, T), dtype=torch.int64, device=dev)
-    n = torch.empty((B, nb), dtype=torch.int32, device=dev)
-    score, ctc, lms = (torch.empty((B, nb), dtype=torch.float32, device=dev) for _ in range(3))
+    B, T, V, roff, in_len, workspace, ids, n, score = _beam_args("ctc_beam_search_lm", logits3d, lse, cand_id, cand_lp, in_len, beam, n_best,
+                                                                 pack, workspace)
+    uni, table, capacity, max_probe, order_lm, _ = _lm_args("ctc_beam_search_lm", lm, lm_weight, logits3d.device, "logits", V)
+    ctc, lms = torch.empty_like(score), torch.empty_like(score)
     check(lib().js2t_ctc_beam_search_lm(_p(logits3d), dt_code(logits3d), _p(lse), _p(cand_id), _p(cand_lp), _p(in_len), _p(uni), _p(table),
                                         capacity, max_probe, order_lm, _p(ids), _p(n), _p(score), _p(ctc), _p(lms), _p(workspace), B, T, V,
                                         beam, cand_id.shape[1], n_best, blank, pad, int(bos), int(eos), float(lm_weight),
                                         float(length_bonus), roff, _stream()), "js2t_ctc_beam_search_lm")
     return ids, n, score, ctc, lms
+
+
+def _nbest_args(who, ids, n, score, N, scores, R=None):
+    """The checks of an n-best list - ids i64 [B, N, T] or [R, T], n i32 and score f32 of R = B * N hypotheses - for the two entry
+    points that re-rank one.  R: the count the caller's logits fix; None: the list itself says it.  Returns (R, B); `who` names the
+    caller in the errors and `scores` its score."""
+    if N < 1:  # (no [B, N] to allocate for the library to refuse)
+        raise Js2tError(f"{who}: N {N} outside 1..32")
+    ids_ok = ids.dim() in (2, 3) and ids.dtype == torch.int64 and ids.is_contiguous()
+    if R is None and ids_ok:
+        R = ids.numel() // ids.shape[-1] if ids.shape[-1] else n.numel()
+    if R is not None and R % N:
+        raise Js2tError(f"{who}: {R} hypotheses are no multiple of N = {N}")
+    if not ids_ok or ids.numel() != R * ids.shape[-1]:
+        raise Js2tError(f"{who}: contiguous i64 ids [{'B' if R is None else R // N}, {N}, T] expected, got {ids.dtype} {tuple(ids.shape)}")
+    if n.dtype != torch.int32 or n.numel() != R or not n.is_contiguous() or score.dtype != torch.float32 or score.numel() != R \
+            or not score.is_contiguous():
+        raise Js2tError(f"{who}: contiguous i32 lengths and f32 {scores} of {R} hypotheses expected, got {n.dtype} {tuple(n.shape)} and "
+                        f"{score.dtype} {tuple(score.shape)}")
+    return R, R // N
+
+
+def _nbest_out(who, out, R, Lp, B, N, dev, tok=True, tok_optional=False):
+    """The four outputs of a re-ranking - per-token values f32 [R, Lp], two scores f32 [R], order i32 [B, N] - fresh ones (the
+    first None without `tok`), or the caller's `out`, checked; tok_optional: its first may be None."""
+    want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
+    if out is None:
+        return (torch.empty((R, max(Lp, 0)), dtype=torch.float32, device=dev) if tok else None,
+                *(torch.empty(s, dtype=d, device=dev) for s, d in want[1:]))
+    given = [(t, w) for t, w in zip(out, want) if not (tok_optional and t is None and w is want[0])]
+    if len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in given):
+        raise Js2tError(f"{who}: out = contiguous (f32 [{R}, {Lp}]{' or None' if tok_optional else ''}, f32 [{R}], f32 [{R}], i32 [{B}, {N}]) "
+                        "expected")
+    return out
 
 
 def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, out=None):
@@ -905,26 +935,8 @@ def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, ou
     N = int(N)
     if R and (logits3d.stride(2) != 1 or logits3d.stride(1) != V or logits3d.stride(0) != Lp * V):
         raise Js2tError(f"rescore: logits with dense rows expected, got strides {logits3d.stride()} for {tuple(logits3d.shape)}")
-    if N < 1:  # (no [B, N] to allocate for the library to refuse)
-        raise Js2tError(f"rescore: N {N} outside 1..32")
-    if R % N:
-        raise Js2tError(f"rescore: {R} hypotheses are no multiple of N = {N}")
-    B = R // N
-    if ids.dim() not in (2, 3) or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != R * ids.shape[-1]:
-        raise Js2tError(f"rescore: contiguous i64 ids [{B}, {N}, T] expected, got {ids.dtype} {tuple(ids.shape)}")
-    if n.dtype != torch.int32 or n.numel() != R or not n.is_contiguous() or ctc_score.dtype != torch.float32 \
-            or ctc_score.numel() != R or not ctc_score.is_contiguous():
-        raise Js2tError(f"rescore: contiguous i32 lengths and f32 CTC scores of {R} hypotheses expected, got {n.dtype} "
-                        f"{tuple(n.shape)} and {ctc_score.dtype} {tuple(ctc_score.shape)}")
-    dev = logits3d.device
-    if out is None:
-        out = (torch.empty((R, Lp), dtype=torch.float32, device=dev), torch.empty((R, ), dtype=torch.float32, device=dev),
-               torch.empty((R, ), dtype=torch.float32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev))
-    else:
-        want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
-        if len(out) != 4 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
-            raise Js2tError(f"rescore: out = contiguous (f32 [{R}, {Lp}], f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
-    tok_lp, att, score, order = out
+    R, B = _nbest_args("rescore", ids, n, ctc_score, N, "CTC scores", R)
+    tok_lp, att, score, order = _nbest_out("rescore", out, R, Lp, B, N, logits3d.device)
     check(lib().js2t_rescore(_p(logits3d), dt_code(logits3d), _p(ids), ids.shape[-1], _p(n), _p(ctc_score), _p(tok_lp), _p(att), _p(score),
                              _p(order), B, N, Lp, V, int(eos), float(ctc_weight), _stream()), "js2t_rescore")
     return tok_lp, att, score, order
@@ -943,43 +955,11 @@ def ngram_rescore(ids, n, base_score, N: int, lm, bos: int, eos: int, lm_weight:
     out: the output tensors to write instead of fresh ones: (lm_tok or None, lm_score, score, order), contiguous."""
     _dev(ids, n, base_score, *(t for t in (out or ()) if t is not None))
     N = int(N)
-    if N < 1:  # (no [B, N] to allocate for the library to refuse)
-        raise Js2tError(f"ngram_rescore: N {N} outside 1..32")
-    if ids.dim() not in (2, 3) or ids.dtype != torch.int64 or not ids.is_contiguous():
-        raise Js2tError(f"ngram_rescore: contiguous i64 ids [B, {N}, T] expected, got {ids.dtype} {tuple(ids.shape)}")
+    R, B = _nbest_args("ngram_rescore", ids, n, base_score, N, "scores")
     T = ids.shape[-1]
-    R = ids.numel() // T if T else n.numel()
-    if R % N:
-        raise Js2tError(f"ngram_rescore: {R} hypotheses are no multiple of N = {N}")
-    B = R // N
-    if n.dtype != torch.int32 or n.numel() != R or not n.is_contiguous() or base_score.dtype != torch.float32 \
-            or base_score.numel() != R or not base_score.is_contiguous():
-        raise Js2tError(f"ngram_rescore: contiguous i32 lengths and f32 scores of {R} hypotheses expected, got {n.dtype} "
-                        f"{tuple(n.shape)} and {base_score.dtype} {tuple(base_score.shape)}")
     Lp = T + 1 if Lp is None else int(Lp)
-    dev = ids.device
-    if lm is None:
-        if float(lm_weight) != 0.0 or V is None:
-            raise Js2tError("ngram_rescore: without an lm, lm_weight 0 and V expected")
-        uni = table = None
-        capacity, max_probe, order_lm = 0, 1, 1
-    else:
-        if lm.uni_dev is None or lm.uni_dev.device != dev:
-            raise Js2tError(f"ngram_rescore: the lm is on {lm.device}, the hypotheses on {dev}: lm.to(device) first")
-        if V is not None and int(V) != lm.V:
-            raise Js2tError(f"ngram_rescore: the lm is over {lm.V} ids, V = {V}")
-        uni, table, V = lm.uni_dev, (lm.table_dev if lm.capacity else None), lm.V
-        capacity, max_probe, order_lm = lm.capacity, lm.max_probe, lm.order
-    if out is None:
-        out = (torch.empty((R, max(Lp, 0)), dtype=torch.float32, device=dev) if want_tokens else None,
-               torch.empty((R, ), dtype=torch.float32, device=dev), torch.empty((R, ), dtype=torch.float32, device=dev),
-               torch.empty((B, N), dtype=torch.int32, device=dev))
-    else:
-        want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
-        given = [(t, w) for t, w in zip(out, want) if t is not None or w is not want[0]]  # lm_tok alone may be None
-        if len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in given):
-            raise Js2tError(f"ngram_rescore: out = contiguous (f32 [{R}, {Lp}] or None, f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
-    lm_tok, lm_score, score, order = out
+    uni, table, capacity, max_probe, order_lm, V = _lm_args("ngram_rescore", lm, lm_weight, ids.device, "hypotheses", V, own_V=True)
+    lm_tok, lm_score, score, order = _nbest_out("ngram_rescore", out, R, Lp, B, N, ids.device, tok=want_tokens, tok_optional=True)
     check(lib().js2t_ngram_rescore(_p(ids), T, _p(n), _p(base_score), _p(uni), _p(table), capacity, max_probe, order_lm, _p(lm_tok),
                                    _p(lm_score), _p(score), _p(order), B, N, Lp, int(V), int(bos), int(eos), float(lm_weight),
                                    float(length_bonus), _stream()), "js2t_ngram_rescore")

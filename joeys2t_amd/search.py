@@ -515,12 +515,39 @@ def _lm_fusion_arg(who, lm_fusion, rerank):
     return lm_fusion == "search"
 
 
-def _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, beam_size, N, lm, lm_weight, length_bonus):
-    """ops.ctc_beam_search_lm over the model's vocabulary (blank = BOS), the lm moved to the device if need be"""
+def _ctc_first_pass(model, batch, who, beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=False):
+    """The first pass of the two CTC decoders (inside their no_grad): encode once, project, pick the candidates of every frame and
+    search for the N best prefixes (blank = BOS) - `fused`: with the LM in the beam (ops.ctc_beam_search_lm over the model's
+    vocabulary, the lm moved to the device if need be).  Returns (ids i64 [B, N, T], n i32 [B, N], ctc f32 [B, N] the pure CTC score,
+    score f32 [B, N] the search's own: ctc itself unless fused, (B, T, V), [encoder output, its mask] with want_encoder)."""
+    from joeys2t_amd.alignment import _ctc_frames
+    ctc_out, _, in_len, *enc = _ctc_frames(model, batch, who=who, want_lse=False, want_encoder=want_encoder)
+    B, T, V = ctc_out.shape
+    logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
+    cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+    if not fused:
+        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
+        return ids, n, ctc, ctc, (B, T, V), enc
     if lm is not None and lm.device != logits.device:
         lm.to(logits.device)
-    return ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm, model.bos_index,
-                                  model.eos_index, lm_weight, length_bonus)
+    ids, n, score, ctc, _ = ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm,
+                                                   model.bos_index, model.eos_index, lm_weight, length_bonus)
+    return ids, n, ctc, score, (B, T, V), enc
+
+
+def _first_rows(order, n_best, N):
+    """(rows [B * n_best] into the flat [B * N] list, slots i64 [B, n_best]) of the n_best first of every utterance by `order`"""
+    slot = order[:, :n_best].to(torch.int64)
+    B = order.shape[0]
+    return (slot + torch.arange(B, device=order.device)[:, None] * N).reshape(B * n_best), slot
+
+
+def _nbest_numpy(ids, n, score):
+    """The decoders' return layout from device rows ids [R, T] (any leading shape), n [R], score [R]: NumPy ids i64 [R, L] cut to the
+    longest hypothesis (L at least 1), scores f32 [R, 1], lengths i64 [R]"""
+    n = n.cpu().numpy().astype(np.int64).reshape(-1)
+    L = max(int(n.max()) if n.size else 0, 1)
+    return np.ascontiguousarray(ids.cpu().numpy().reshape(n.size, ids.shape[-1])[:, :L]), score.cpu().numpy().reshape(n.size, 1), n
 
 
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
@@ -539,7 +566,6 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     prunes by ctc + lm_weight * lm + length_bonus * n, so a labelling the LM prefers survives where the CTC score alone would have
     dropped it; the returned scores are the kernel's final scores (EOS term included).  There is no list to re-rank: n_rescore is
     refused."""
-    from joeys2t_amd.alignment import _ctc_frames
     rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
     fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
     if not 1 <= n_best <= beam_size:
@@ -547,51 +573,22 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     if fused:
         if n_rescore is not None:
             raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
-        with torch.no_grad():
-            ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
-            B, T, V = ctc_out.shape
-            logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-            cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-            ids, n, score, _, _ = _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, int(beam_size), int(n_best), lm, lm_weight,
-                                                  length_bonus)
-        n = n.cpu().numpy().astype(np.int64).reshape(B * n_best)
-        L = max(int(n.max()) if n.size else 0, 1)
-        return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
-    if rerank:
+    elif rerank:
         n_rescore = int(beam_size if n_rescore is None else n_rescore)
         if not n_best <= n_rescore <= beam_size:
             raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
-        return _ctc_beam_search_lm(model, batch, int(beam_size), int(n_best), candidates, lm, lm_weight, length_bonus, n_rescore)
-    if n_rescore is not None:
+    elif n_rescore is not None:
         raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
+    beam_size, n_best = int(beam_size), int(n_best)
+    N = n_rescore if rerank and not fused else n_best  # the slots searched for
     with torch.no_grad():
-        ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
-        B, T, V = ctc_out.shape
-        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-        ids, n, score = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, int(beam_size), int(n_best), model.bos_index,
-                                            model.pad_index)
-    n = n.cpu().numpy().astype(np.int64).reshape(B * n_best)
-    L = max(int(n.max()) if n.size else 0, 1)
-    return np.ascontiguousarray(ids.cpu().numpy().reshape(B * n_best, T)[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
-
-
-def _ctc_beam_search_lm(model, batch, beam_size, n_best, candidates, lm, lm_weight, length_bonus, N):
-    """ctc_beam_search with the N best prefixes re-ranked by the n-gram LM and the length bonus; the same return layout"""
-    from joeys2t_amd.alignment import _ctc_frames
-    with torch.no_grad():
-        ctc_out, _, in_len = _ctc_frames(model, batch, who="ctc_beam_search", want_lse=False)
-        B, T, V = ctc_out.shape
-        dev = ctc_out.device
-        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
-        _, _, score, order = _ngram_rerank(model, ids, n, ctc, N, lm, lm_weight, length_bonus, dev)  # Lp = T + 1: no length to read
-        rows = (order[:, :n_best].to(torch.int64) + torch.arange(B, device=dev)[:, None] * N).reshape(B * n_best)
-        ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score[rows]
-    n = n.cpu().numpy().astype(np.int64)
-    L = max(int(n.max()) if n.size else 0, 1)
-    return np.ascontiguousarray(ids.cpu().numpy()[:, :L]), score.cpu().numpy().reshape(B * n_best, 1), n
+        ids, n, ctc, score, (B, T, _), _ = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
+                                                           length_bonus)
+        if rerank and not fused:  # the N best re-ranked by the n-gram LM and the length bonus, the n_best first of them returned
+            _, _, score, order = _ngram_rerank(model, ids, n, ctc, N, lm, lm_weight, length_bonus, ids.device)  # Lp = T + 1: no length to read
+            rows, _ = _first_rows(order, n_best, N)
+            ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score[rows]
+    return _nbest_numpy(ids, n, score)
 
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
@@ -615,7 +612,6 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     lm_fusion="search": the first pass is the LM-fused beam search (js2t_ctc_beam_search_lm with n_best = n_rescore), so the list
     that is re-scored already holds the labellings the LM prefers; its pure CTC score (out_ctc) is js2t_rescore's CTC score, the
     rest is unchanged and "ctc_rank" is the slot in the fused list."""
-    from joeys2t_amd.alignment import _ctc_frames
     rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
     fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
     n_rescore = beam_size if n_rescore is None else n_rescore
@@ -627,16 +623,9 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         raise ValueError(f"ctc_attention_rescore: ctc_weight {ctc_weight} outside [0, 1]")
     N = n_rescore
     with torch.no_grad():
-        ctc_out, _, in_len, encoder_output, src_mask = _ctc_frames(model, batch, who="ctc_attention_rescore", want_lse=False,
-                                                                   want_encoder=True)
-        B, T, V = ctc_out.shape
-        dev = ctc_out.device
-        logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-        cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-        if fused:
-            ids, n, _, ctc, _ = _ctc_beam_fused(model, logits, lse, cand_id, cand_lp, in_len, beam_size, N, lm, lm_weight, length_bonus)
-        else:
-            ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
+        ids, n, ctc, _, (B, T, _), (encoder_output, src_mask) = _ctc_first_pass(model, batch, "ctc_attention_rescore", beam_size, N, candidates,
+                                                                                fused, lm, lm_weight, length_bonus, want_encoder=True)
+        dev = ids.device
         Lp = int(n.max().item()) + 1 if n.numel() else 1  # the one host read: it sizes the decoder pass
         ids2 = ids.view(B * N, T)
         trg_input = torch.cat([torch.full((B * N, 1), model.bos_index, dtype=torch.int64, device=dev), ids2[:, :Lp - 1]], dim=1).contiguous()
@@ -648,12 +637,8 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         if rerank:
             lm_tok, lm_score, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, dev, Lp=Lp,
                                                            want_tokens=return_parts)
-        slot = order[:, :n_best].to(torch.int64)
-        rows = (slot + torch.arange(B, device=dev)[:, None] * N).reshape(B * n_best)  # the n_best first of every utterance
-        out_n = n.view(B * N)[rows].to(torch.int64).cpu().numpy()
-        L = max(int(out_n.max()) if out_n.size else 0, 1)
-        out_ids = np.ascontiguousarray(ids2[rows].cpu().numpy()[:, :L])
-        out_score = score[rows].cpu().numpy().reshape(B * n_best, 1)
+        rows, slot = _first_rows(order, n_best, N)  # the n_best first of every utterance
+        out_ids, out_score, out_n = _nbest_numpy(ids2[rows], n.view(B * N)[rows], score[rows])
         if not return_parts:
             return out_ids, out_score, out_n
         tl = tok_lp[rows].cpu().numpy()
