@@ -570,6 +570,50 @@ int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* lse, const 
                             int64_t blank, int64_t pad, int64_t bos, int64_t eos, float lm_weight, float length_bonus,
                             const int32_t* row_offsets, js2t_stream stream);
 
+/* EXTENSION (the reference has no edit distance on the device): unit-cost Levenshtein distances of pairs of rows of i64 ids, one wave
+ * per pair.  Row r of `a` lies at a + r * a_stride and has a_len[r] (i32) ids; it is compared with row r / group of `b`, at
+ * b + (r / group) * b_stride with b_len[r / group] ids: group = 1 pairs the rows one to one, group = N compares the N hypotheses of an
+ * utterance with its one reference.  Ids are compared as full 64-bit values (5 and 2^40 + 5 differ), no id is a sentinel, and only
+ * a[r][0 .. a_len[r] - 1] and b[..][0 .. b_len[..] - 1] are read.
+ * dist i32 [R]: the distance; exactly -1 where either length is negative, a_len[r] > a_max or b_len[r / group] > b_max, and nothing
+ * of such a pair's rows is read.  a_max / b_max: the largest length a row of a / b may have (the width of the table): it is what the
+ * host can check without reading the lengths.
+ * JS2T_EDIT_MAX_LEN is the largest supported length: the DP keeps one 16-bit boundary cell per position of the longer row in 4 KB of
+ * LDS per wave (joeys2t_amd/csrc/editdist.hpp).  An a_max or b_max above it is an argument error, never a truncated result;
+ * js2t_edit_max_len returns it.
+ * Limits: group >= 1, 0 <= a_max, b_max <= JS2T_EDIT_MAX_LEN, 0 <= R < 2^31, strides >= 0 (a stride of 0 compares every row with one row);
+ * R = 0 returns 0.
+ * One launch; no workspace, no atomics, no allocation, no synchronisation: bit-reproducible, capturable. */
+#define JS2T_EDIT_MAX_LEN 2047
+int js2t_edit_max_len(void);
+int js2t_edit_distance(const int64_t* a, int64_t a_stride, const int32_t* a_len, const int64_t* b, int64_t b_stride,
+                       const int32_t* b_len, int32_t* dist, int64_t R, int64_t group, int64_t a_max, int64_t b_max, js2t_stream stream);
+
+/* EXTENSION (the reference has no n-best list): minimum-Bayes-risk ranking of an n-best list - the hypothesis with the smallest
+ * expected edit distance to the rest of the list, the list's normalised scores serving as the posterior, instead of the one with the
+ * highest score.  It sits where js2t_rescore and js2t_ngram_rescore sit and takes their layout, so that it composes with them:
+ * R = B * N hypotheses, N slots per utterance; the labels of hypothesis r at ids + r * ids_stride; n i32 [R] label counts; score f32
+ * [R] the last stage's score (the CTC score, js2t_rescore's or js2t_ngram_rescore's), natural logarithms.
+ * Dead slots: score = -inf, n < 0 or n > Lp - 1 (the rule of the list), and a score that is NaN or +inf - neither is a log mass.
+ * A dead slot has posterior 0 and risk +inf, dist is -1 in its row and its column, the diagonal included, and none of its ids are
+ * read.  Ids behind n[r] are never read.
+ * dist i32 [B, N, N]: dist[b, i, j] for live i, j = the Levenshtein distance of their labels (js2t_edit_distance's: unit costs, full
+ * 64-bit ids); the diagonal is exactly 0; a pair is computed once and stored at (i, j) and (j, i): symmetric by construction.
+ * posterior f32 [R], over the live slots of an utterance: z_k = scale * score_k rounded to f32, m = the maximum of z, e_k =
+ * exp(z_k - m) (exactly 1 where z_k = m), S = the sum of e_k in ascending slot order, p_k = e_k / S.  scale < 1 flattens the
+ * posterior, a large scale makes it one-hot: the ranking is then by the distance to the best-scored hypothesis.
+ * risk f32 [R]: risk_i = the sum over live j, in ascending j, of p_j * (float)dist[b, i, j], each product rounded to f32 before it is
+ * added (no contraction): one fixed order, the same bits alone and in a batch, on every run and under graph replay.
+ * order i32 [B, N]: the slots by ASCENDING risk (nbest.hpp's rank on the key -risk): equal risks keep slot order, dead slots come
+ * last in slot order, an utterance without a live slot gets the identity: always a permutation of 0 .. N-1.  posterior / risk stay
+ * in input slot order.
+ * Limits, all checked before anything is launched: 1 <= N <= 32, Lp >= 1, Lp - 1 <= JS2T_EDIT_MAX_LEN, ids_stride >= Lp - 1, scale
+ * finite and > 0, B * N * N < 2^31; B = 0 returns 0.
+ * Two launches on `stream` (one when N = 1: there is no pair); no workspace beyond dist, no atomics, no allocation, no
+ * synchronisation: capturable. */
+int js2t_mbr_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* score, int32_t* dist, float* posterior,
+                     float* risk, int32_t* order, int64_t B, int32_t N, int64_t Lp, float scale, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

@@ -1,6 +1,6 @@
 // The rules the n-best entry points share (EXTENSION; the reference has no n-best list): js2t_ctc_beam_search(_lm) writes the list,
-// js2t_rescore and js2t_ngram_rescore re-rank it, and they compose because each of these rules exists once, here.  The semantics
-// are stated in the header; rescore.hip, ngram.hip and ctc_beam.hip are the files that apply them.
+// js2t_rescore, js2t_ngram_rescore and js2t_mbr_rescore re-rank it, and they compose because each of these rules exists once, here.
+// The semantics are stated in the header; rescore.hip, ngram.hip, ctc_beam.hip and mbr.hip are the files that apply them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -23,6 +23,25 @@ def edit_distance(a: Sequence, b: Sequence) -> int:
     return prev[-1]
 
 
+def token_errors(hyp_ids, hyp_len, ref_ids, ref_len, group: int = 1, return_dist: bool = False):
+    """Label errors of a decode without a host loop (EXTENSION; js2t_edit_distance): device tensors hyp_ids i64 [R, Wh] with lengths
+    hyp_len i32 [R] and ref_ids i64 [ceil(R / group), Wr] with lengths ref_len i32; hypothesis r is compared with reference
+    r // group.  Returns (total edit distance, total reference labels) as Python ints after ONE read: their ratio is the token error
+    rate.  group = N compares the N hypotheses of every utterance with its one reference; a reference's labels then count once per
+    hypothesis, and return_dist adds a third element, the distances i64 [R] as NumPy (from the same read) - the smallest of an
+    utterance's N gives the oracle error rate of the list.  A negative length, or one beyond its table's width, is refused."""
+    import torch
+    from joeys2t_amd import ops
+    dist = ops.edit_distance(hyp_ids, hyp_len, ref_ids, ref_len, group=group)
+    R = dist.numel()
+    ref_rows = torch.arange(R, device=dist.device) // int(group)
+    got = torch.cat([dist.to(torch.int64), ref_len.to(torch.int64)[ref_rows].sum().reshape(1)]).cpu().numpy()  # the one read
+    d, n_ref = got[:R], int(got[R])
+    if (d < 0).any():
+        raise ValueError(f"token_errors: {int((d < 0).sum())} of {R} pairs have a length that is negative or beyond its table's width")
+    return (int(d.sum()), n_ref, d) if return_dist else (int(d.sum()), n_ref)
+
+
 def wer(hypotheses: List[str], references: List[str], tokenizer: Callable = None) -> float:
     """Corpus-level word error rate: sum of edit distances / sum of reference lengths * 100 (metrics.py:110-131)."""
     tok = tokenizer or (lambda s: s.split())

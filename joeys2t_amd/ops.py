@@ -966,6 +966,70 @@ def ngram_rescore(ids, n, base_score, N: int, lm, bos: int, eos: int, lm_weight:
     return lm_tok, lm_score, score, order
 
 
+def edit_max_len() -> int:
+    """JS2T_EDIT_MAX_LEN: the longest row js2t_edit_distance and js2t_mbr_rescore take"""
+    return lib().js2t_edit_max_len()
+
+
+def _id_rows(who, what, t, t_len):
+    """The checks of one table of id rows for edit_distance - i64 [rows, width], the ids of a row dense, the rows any number of
+    elements apart (a strided view and any storage offset are fine), lengths i32 [rows] contiguous.  Returns (rows, row stride)."""
+    if t.dim() != 2 or t.dtype != torch.int64 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < 0):
+        raise Js2tError(f"{who}: {what} = i64 [rows, width] with dense rows expected, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    if t_len.dtype != torch.int32 or t_len.dim() != 1 or t_len.numel() != t.shape[0] or not t_len.is_contiguous():
+        raise Js2tError(f"{who}: {what}_len = contiguous i32 [{t.shape[0]}] expected, got {t_len.dtype} {tuple(t_len.shape)}")
+    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def edit_distance(a, a_len, b, b_len, group: int = 1, out=None):
+    """Unit-cost Levenshtein distances of pairs of id rows (js2t_edit_distance): a i64 [R, Wa] with lengths a_len i32 [R], b i64
+    [ceil(R / group), Wb] with lengths b_len; row r of a is compared with row r // group of b (group = N: the N hypotheses of an
+    utterance against its one reference).  The ids of a row are dense, the rows any number of elements apart: a strided view is
+    fine.  Ids are compared as 64-bit values, nothing behind a row's length is read.  Returns dist i32 [R]: -1 where a length is
+    negative or above its table's width.  Rows wider than edit_max_len() are refused.
+    out: the i32 [R] tensor to write instead of a fresh one."""
+    _dev(a, a_len, b, b_len, out)
+    group = int(group)
+    if group < 1:
+        raise Js2tError(f"edit_distance: group {group} below 1")
+    R, a_stride = _id_rows("edit_distance", "a", a, a_len)
+    Rb, b_stride = _id_rows("edit_distance", "b", b, b_len)
+    if Rb != -(-R // group):
+        raise Js2tError(f"edit_distance: {R} rows in groups of {group} need {-(-R // group)} rows of b, got {Rb}")
+    if out is None:
+        out = torch.empty((R, ), dtype=torch.int32, device=a.device)
+    elif tuple(out.shape) != (R, ) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise Js2tError(f"edit_distance: out = contiguous i32 [{R}] expected")
+    check(lib().js2t_edit_distance(_p(a), a_stride, _p(a_len), _p(b), b_stride, _p(b_len), _p(out), R, group, a.shape[1], b.shape[1],
+                                   _stream()), "js2t_edit_distance")
+    return out
+
+
+def mbr_rescore(ids, n, score, N: int, scale: float = 1.0, Lp: int = None, out=None):
+    """Minimum-Bayes-risk ranking of an n-best list (js2t_mbr_rescore): ids i64 [B, N, T] or [R, T] (ctc_beam_search's table as it
+    is), n i32 [B, N] or [R] label counts, score f32 [B, N] or [R] the last stage's score (log domain).  Lp bounds the lengths (a slot
+    with n > Lp - 1 is dead); default T + 1, which no length exceeds - no host read is needed.
+    Returns (dist i32 [B, N, N]: the edit distance of every pair of live slots, 0 on the diagonal; posterior f32 [R]: softmax of
+    scale * score over the live slots of the utterance; risk f32 [R]: the expected distance to the list, sum_j posterior_j *
+    dist[i, j]; order i32 [B, N]: the input slot of every utterance's k-th best by ASCENDING risk, equal risks in slot order).  Dead
+    slots (score -inf, NaN or +inf, n outside 0 .. Lp - 1): posterior 0, risk +inf, dist -1 in row and column, ranked last.
+    out: the four output tensors to write instead of fresh ones (contiguous, those shapes and dtypes)."""
+    _dev(ids, n, score, *(out or ()))
+    N = int(N)
+    R, B = _nbest_args("mbr_rescore", ids, n, score, N, "scores")
+    T = ids.shape[-1]
+    Lp = T + 1 if Lp is None else int(Lp)
+    want = (((B, N, N), torch.int32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=ids.device) for s, d in want)
+    elif len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
+        raise Js2tError(f"mbr_rescore: out = contiguous (i32 [{B}, {N}, {N}], f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
+    dist, posterior, risk, order = out
+    check(lib().js2t_mbr_rescore(_p(ids), T, _p(n), _p(score), _p(dist), _p(posterior), _p(risk), _p(order), B, N, Lp, float(scale),
+                                 _stream()), "js2t_mbr_rescore")
+    return dist, posterior, risk, order
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the

@@ -20,7 +20,7 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import ctc_attention_rescore, ctc_beam_search, search
+from joeys2t_amd.search import _decision_args, ctc_attention_rescore, ctc_beam_search, search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
@@ -28,7 +28,7 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
             decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
-            length_bonus: float = 0.0, lm_fusion: str = "rescore"):
+            length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -45,7 +45,10 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     lm / lm_weight / length_bonus (EXTENSION): an n-gram LM over the target vocabulary (joeys2t_amd.lm.NGramLM) and a bonus per label,
     handed to the two CTC decoders, which re-rank their n-best list with them on the device; the attention decoder has no place
     for them and refuses them.  lm_fusion="search" (EXTENSION; default "rescore") applies them inside the CTC beam of either CTC
-    decoder instead (shallow fusion, `search.ctc_beam_search`); the attention decoder refuses it too."""
+    decoder instead (shallow fusion, `search.ctc_beam_search`); the attention decoder refuses it too.
+    decision="mbr" / mbr_scale (EXTENSION; default "map"): the two CTC decoders rank their n-best list by minimum Bayes risk - the
+    smallest expected edit distance to the list under the softmax of mbr_scale * score - instead of by score (`search.ctc_beam_search`);
+    the hypotheses of a sentence then come in ascending risk, each with its model score.  The attention decoder refuses them."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
     if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
@@ -55,10 +58,16 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         raise ValueError(f"predict: lm_fusion '{lm_fusion}' is neither 'rescore' nor 'search'")
     if decoder == "attention" and lm_fusion != "rescore":
         raise ValueError("predict: lm_fusion applies to the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
+    mbr, mbr_scale = _decision_args("predict", decision, mbr_scale)
+    if decoder == "attention" and mbr:
+        raise ValueError("predict: decision='mbr' ranks the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
+                         "no such list")
     lm_kw = {} if lm is None and float(lm_weight) == 0.0 and float(length_bonus) == 0.0 else \
         dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
     if lm_fusion != "rescore":
         lm_kw = dict(lm_kw, lm_fusion=lm_fusion)  # (without an lm or a bonus the decoder refuses it)
+    if mbr:
+        lm_kw = dict(lm_kw, decision="mbr", mbr_scale=mbr_scale)
     ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}

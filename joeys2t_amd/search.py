@@ -515,6 +515,25 @@ def _lm_fusion_arg(who, lm_fusion, rerank):
     return lm_fusion == "search"
 
 
+def _decision_args(who, decision, mbr_scale):
+    """(rank by minimum Bayes risk?, mbr_scale) of the decision options of the two CTC decoders; refused before the model is touched"""
+    if decision not in ("map", "mbr"):
+        raise ValueError(f"{who}: decision '{decision}' is neither 'map' nor 'mbr'")
+    mbr_scale = float(mbr_scale)
+    if not (math.isfinite(mbr_scale) and mbr_scale > 0.0):
+        raise ValueError(f"{who}: mbr_scale {mbr_scale} not finite and above 0")
+    if decision == "map" and mbr_scale != 1.0:
+        raise ValueError(f"{who}: mbr_scale {mbr_scale} with decision='map' (it scales the posterior of decision='mbr')")
+    return decision == "mbr", mbr_scale
+
+
+def _map_rank(order, B, N, dev):
+    """i64 [B, N]: the rank of every slot by the model score - the inverse of the last stage's `order`; None: the list came best
+    first, the rank of a slot is the slot"""
+    slots = torch.arange(N, device=dev, dtype=torch.int64).expand(B, N)
+    return slots if order is None else torch.empty((B, N), dtype=torch.int64, device=dev).scatter_(1, order.to(torch.int64), slots)
+
+
 def _ctc_first_pass(model, batch, who, beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=False):
     """The first pass of the two CTC decoders (inside their no_grad): encode once, project, pick the candidates of every frame and
     search for the N best prefixes (blank = BOS) - `fused`: with the LM in the beam (ops.ctc_beam_search_lm over the model's
@@ -551,7 +570,8 @@ def _nbest_numpy(ids, n, score):
 
 
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
-                    length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore"):
+                    length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore", decision: str = "map",
+                    mbr_scale: float = 1.0, return_parts: bool = False):
     """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
     `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
     `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
@@ -565,35 +585,55 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     lm_fusion="search" applies the LM and the bonus INSIDE the beam instead (shallow fusion, js2t_ctc_beam_search_lm): every frame
     prunes by ctc + lm_weight * lm + length_bonus * n, so a labelling the LM prefers survives where the CTC score alone would have
     dropped it; the returned scores are the kernel's final scores (EOS term included).  There is no list to re-rank: n_rescore is
-    refused."""
+    refused.
+    decision="mbr" (default "map": everything above) returns the minimum-Bayes-risk choice instead of the best-scored one: the
+    `n_rescore` (default: beam_size) best are searched for and scored exactly as above - n_rescore is then accepted without an LM
+    too, and with lm_fusion="search", where it is the fused search's n_best - and ranked on the device by their expected edit
+    distance to the list under the posterior softmax(mbr_scale * score) (js2t_mbr_rescore); the n_best first are returned.  The rows
+    of an utterance are then in ASCENDING RISK, not in descending score; the scores column keeps each row's model score, the value
+    the row would carry with decision="map".  Still no host read before the final copy.  A hypothesis of more than
+    ops.edit_max_len() labels takes no part (it is ranked last).
+    return_parts: a fourth element, a dict of per-returned-row NumPy data: "map_rank" i64 [B * n_best] (the row's rank within its
+    utterance by the model score) and, with decision="mbr", "risk" and "posterior" f32 [B * n_best]."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
     fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
+    mbr, mbr_scale = _decision_args("ctc_beam_search", decision, mbr_scale)
     if not 1 <= n_best <= beam_size:
         raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
-    if fused:
+    if fused and not mbr:
         if n_rescore is not None:
             raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
-    elif rerank:
+    elif rerank or mbr:
         n_rescore = int(beam_size if n_rescore is None else n_rescore)
         if not n_best <= n_rescore <= beam_size:
             raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
     elif n_rescore is not None:
         raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
     beam_size, n_best = int(beam_size), int(n_best)
-    N = n_rescore if rerank and not fused else n_best  # the slots searched for
+    N = n_rescore if mbr or (rerank and not fused) else n_best  # the slots searched for
     with torch.no_grad():
         ids, n, ctc, score, (B, T, _), _ = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
                                                            length_bonus)
+        order = None  # (the search returns its list best first)
         if rerank and not fused:  # the N best re-ranked by the n-gram LM and the length bonus, the n_best first of them returned
             _, _, score, order = _ngram_rerank(model, ids, n, ctc, N, lm, lm_weight, length_bonus, ids.device)  # Lp = T + 1: no length to read
+        map_rank = _map_rank(order, B, N, ids.device) if return_parts else None
+        if mbr:  # the list ranked by its expected edit distance instead; Lp from the table's width: no length to read
+            _, posterior, risk, order = ops.mbr_rescore(ids, n, score.reshape(B * N), N, mbr_scale, Lp=min(T, ops.edit_max_len()) + 1)
+        if order is not None:
             rows, _ = _first_rows(order, n_best, N)
-            ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score[rows]
-    return _nbest_numpy(ids, n, score)
+            ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score.reshape(B * N)[rows]
+        if not return_parts:
+            return _nbest_numpy(ids, n, score)
+        parts = {"map_rank": (map_rank.reshape(B * N)[rows] if order is not None else map_rank.reshape(B * N)).cpu().numpy()}
+        if mbr:
+            parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
+    return (*_nbest_numpy(ids, n, score), parts)
 
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
                           n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
-                          length_bonus: float = 0.0, lm_fusion: str = "rescore"):
+                          length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0):
     """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
     of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
     over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
@@ -611,9 +651,15 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     score of js2t_ngram_rescore, whose ranking decides; the parts gain "lm" f32 [B * n_best] and "lm_token_log_probs".
     lm_fusion="search": the first pass is the LM-fused beam search (js2t_ctc_beam_search_lm with n_best = n_rescore), so the list
     that is re-scored already holds the labellings the LM prefers; its pure CTC score (out_ctc) is js2t_rescore's CTC score, the
-    rest is unchanged and "ctc_rank" is the slot in the fused list."""
+    rest is unchanged and "ctc_rank" is the slot in the fused list.
+    decision="mbr" (default "map": everything above): the n_rescore hypotheses are scored exactly as above and then ranked on the
+    device by their expected edit distance to the list under the posterior softmax(mbr_scale * final score) (js2t_mbr_rescore); the
+    n_best first are returned.  The rows of an utterance are then in ASCENDING RISK, not in descending score; the scores column keeps
+    each row's final model score.  The parts gain "risk" and "posterior" f32 [B * n_best] and "map_rank" i64 [B * n_best], the row's
+    rank within its utterance by the final model score.  The host read that sizes the decoder pass stays the only one."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
     fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
+    mbr, mbr_scale = _decision_args("ctc_attention_rescore", decision, mbr_scale)
     n_rescore = beam_size if n_rescore is None else n_rescore
     beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
     if not 1 <= n_best <= n_rescore <= beam_size <= 32:
@@ -637,6 +683,9 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         if rerank:
             lm_tok, lm_score, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, dev, Lp=Lp,
                                                            want_tokens=return_parts)
+        if mbr:  # the same list and scores, ranked by the expected edit distance instead
+            map_rank = _map_rank(order, B, N, dev) if return_parts else None
+            _, posterior, risk, order = ops.mbr_rescore(ids, n, score, N, mbr_scale, Lp=Lp)
         rows, slot = _first_rows(order, n_best, N)  # the n_best first of every utterance
         out_ids, out_score, out_n = _nbest_numpy(ids2[rows], n.view(B * N)[rows], score[rows])
         if not return_parts:
@@ -649,4 +698,7 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
             ll = lm_tok[rows].cpu().numpy()
             parts["lm"] = lm_score[rows].cpu().numpy()
             parts["lm_token_log_probs"] = [ll[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)]
+        if mbr:
+            parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
+            parts["map_rank"] = map_rank.reshape(B * N)[rows].cpu().numpy()
     return out_ids, out_score, out_n, parts
