@@ -570,6 +570,82 @@ int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* lse, const 
                             int64_t blank, int64_t pad, int64_t bos, int64_t eos, float lm_weight, float length_bonus,
                             const int32_t* row_offsets, js2t_stream stream);
 
+/* EXTENSION (the reference has no hot words): contextual biasing - CTC prefix beam search with a phrase automaton INSIDE the beam, and
+ * the same count for a finished n-best list.  The LM is a model of the language in general; the phrases say what matters for this
+ * batch (names, product terms).  A rare name is pruned in the frames where it is spoken, so the boost acts in the pruning of every
+ * frame; re-ranking cannot replace it.
+ * The graph.  A set of phrases, each a sequence of ids in 0 .. V-1, compiled on the host (joeys2t_amd/biasing.py does;
+ * joeys2t_amd/csrc/context.hpp reads it) into an Aho-Corasick automaton over the trie of the phrases.  Per node u: depth(u); fail(u) =
+ * the node of the longest proper suffix of u's string that is a trie node, the root if there is none; keep(u) = the depth of the
+ * deepest node on the path root .. u, u included, at which a phrase ends, 0 if there is none.
+ *   ctx_nodes: ctx_n_nodes records of 16 bytes {i32 fail, i32 depth, i32 keep, 0}, 16-byte aligned; node 0 is the root.
+ *   ctx_edges: ctx_capacity entries in js2t_ngram_rescore's entry format under its probing rule (home slot, linear probing with
+ *   wrap-around, ctx_max_probe), 16-byte aligned: the key of the edge (node, token) is the 2-gram key of (node, token) - token + 1 in
+ *   bits 0 .. 15, node + 1 in bits 16 .. 31 - and the entry's first value word holds the child's id as an i32 (the second is 0).
+ *   ctx_max_fail: the largest number of fail links between a node and the root.
+ * The rule.  A prefix y carries (node(y), bank(y)), both i32; the empty prefix carries (root, 0).  Extending y by token c, u = node(y):
+ *   1. if u has a child by c: node = that child, bank unchanged;
+ *   2. otherwise bank += keep(u) - only the node left first banks;
+ *   3. then w = fail(u); while w has no child by c and w != root: w = fail(w);
+ *   4. node = child(w, c) if it exists, else root;
+ *   5. a token outside 0 .. V-1 goes to root and banks keep(u).
+ * In the beam m(y) = bank(y) + depth(node(y)): the pending partial match counts while it is alive and is retracted by the arithmetic
+ * when it fails.  After the last frame ctx(y) = bank(y) + keep(node(y)): a partial match that never completed earns nothing.  Both are
+ * integers - the number of matched tokens - and functions of the label sequence alone, as lm(y) is: a prefix that is pruned and
+ * created again gets the bits of its surviving twin, and the prefix identity of js2t_ctc_beam_search carries over.
+ * Examples, tokens as letters.  Phrases {a b c, c d}: "a b" m 2, ctx 0; "a b c" m 3, ctx 3; "a b c d" m 5, ctx 5 (both occurrences
+ * count by their length); "a b x" m 0; "a a b c" ctx 3.  Phrases {a b, a b c d}: "a b c" m 3, ctx 2; "a b c x" m 2.  Phrases
+ * {a b c d, b c}: "a b c x" m 0 - a limitation, stated and not fixed: an occurrence strictly inside a failed longer match is credited
+ * only if it is a prefix of that match.
+ * Every loop of the walk is bounded by an argument checked on the host - the fail chain by ctx_max_fail, a probe by ctx_max_probe -
+ * and a node id read from the tables is used only inside 0 .. ctx_n_nodes-1: inconsistent tables give a wrong count, never a loop
+ * without end or an address outside the tables; a walk that exhausts its bound ends at root.
+ *
+ * js2t_ctc_beam_search_ctx: the arguments of js2t_ctc_beam_search_lm, the graph, context_weight and out_ctx.  Same workspace.
+ * Ranking key of a frame: key(y) = lae(pb, pnb) + lm_weight * lm(y) + context_weight * (float)m(y) + length_bonus * |y|, each product
+ * rounded to f32, added in that order, a term whose weight is exactly 0 LEFT OUT.  Final score: ctx(y) in place of m(y) and the LM's
+ * EOS term as in js2t_ctc_beam_search_lm; the beam is ranked again by it under the same tie and NaN rule.  pb / pnb / out_ctc stay
+ * pure CTC masses.  out_ctx i32 [B, n_best] = ctx(y) of the returned labelling, what js2t_context_rescore counts for it; 0 in a slot
+ * without a prefix and everywhere when context_weight == 0.
+ * Biasing adds no candidates: a phrase token outside a frame's n_cand (<= 8) candidates is still not proposed.
+ * lm_weight == 0: uni / table are not read and may be NULL, as in js2t_ctc_beam_search_lm.  context_weight == 0: the graph is not
+ * read, ctx_nodes / ctx_edges may be NULL and the other graph arguments are not looked at; ids, lengths and the three scores are the
+ * bits of js2t_ctc_beam_search_lm.  All three weights 0: the bits of js2t_ctc_beam_search.
+ * Limits: those of js2t_ctc_beam_search_lm, context_weight finite, and with context_weight != 0: 2 <= ctx_n_nodes <=
+ * JS2T_CONTEXT_MAX_NODES, 1 <= ctx_max_fail <= JS2T_CONTEXT_MAX_FAIL, V <= JS2T_CONTEXT_MAX_V, ctx_capacity a power of two, 1 <=
+ * ctx_max_probe <= ctx_capacity.  A phrase has at most JS2T_CONTEXT_MAX_LEN tokens (the builder refuses a longer one; a fail chain is
+ * never longer than the longest phrase).  B = 0 returns 0.
+ * One launch; no atomics, no allocation, no synchronisation: bit-reproducible, capturable.
+ *
+ * js2t_context_rescore: sits where js2t_ngram_rescore sits and takes its layout - R = B * N hypotheses, the labels of hypothesis r at
+ * ids + r * ids_stride, n i32 [R], base_score f32 [R] the last stage's score.  ctx i32 [R] = ctx(y) of the labels; score = base_score
+ * + context_weight * (float)ctx, the product rounded to f32; a weight of exactly 0 is LEFT OUT and reads neither the graph nor the ids
+ * (ctx is 0, score is base_score's bits).  Dead slots (base_score = -inf, n < 0 or n > Lp - 1): ctx 0, score -inf, none of their ids
+ * read; ids behind n[r] are never read.  order i32 [B, N]: by score, descending, equal scores in slot order, a NaN as -inf: always a
+ * permutation.  Limits: 1 <= N <= 32, Lp >= 1, ids_stride >= Lp - 1, the graph's as above; B = 0 returns 0.  One launch, capturable.
+ *
+ * js2t_context_walk_host: the same walk on the HOST over host tables, for one sequence of n ids: (node, bank), m and ctx after every
+ * token, i32 [n] each.  No device is touched: it is how the statement the two kernels share is checked without one. */
+#define JS2T_CONTEXT_MAX_NODES 65535
+#define JS2T_CONTEXT_MAX_LEN 32
+#define JS2T_CONTEXT_MAX_FAIL 32
+#define JS2T_CONTEXT_MAX_V 65535
+int js2t_ctc_beam_search_ctx(const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+                             const int64_t* in_len, const float* uni, const void* table, int64_t capacity, int32_t max_probe,
+                             int32_t lm_order, const void* ctx_nodes, const void* ctx_edges, int64_t ctx_capacity,
+                             int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail, int64_t* out_ids, int32_t* out_len,
+                             float* out_score, float* out_ctc, float* out_lm, int32_t* out_ctx, void* workspace, int64_t B, int64_t T,
+                             int64_t V, int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank, int64_t pad, int64_t bos,
+                             int64_t eos, float lm_weight, float context_weight, float length_bonus, const int32_t* row_offsets,
+                             js2t_stream stream);
+int js2t_context_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* base_score, const void* ctx_nodes,
+                         const void* ctx_edges, int64_t ctx_capacity, int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail,
+                         int32_t* ctx, float* score, int32_t* order, int64_t B, int32_t N, int64_t Lp, int64_t V, float context_weight,
+                         js2t_stream stream);
+int js2t_context_walk_host(const int64_t* ids, int64_t n, const void* ctx_nodes, const void* ctx_edges, int64_t ctx_capacity,
+                           int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail, int64_t V, int32_t* out_node,
+                           int32_t* out_bank, int32_t* out_m, int32_t* out_ctx);
+
 /* EXTENSION (the reference has no edit distance on the device): unit-cost Levenshtein distances of pairs of rows of i64 ids, one wave
  * per pair.  Row r of `a` lies at a + r * a_stride and has a_len[r] (i32) ids; it is compared with row r / group of `b`, at
  * b + (r / group) * b_stride with b_len[r / group] ids: group = 1 pairs the rows one to one, group = N compares the N hypotheses of an

@@ -22,11 +22,19 @@
 // ranks the beam again by counting and the back-trace runs in that order.  With LM = false none of it is compiled: that form is
 // what js2t_ctc_beam_search launches.
 //
+// Contextual biasing (js2t_ctc_beam_search_ctx) is the LM form with CTX = true on top: every prefix carries context.hpp's state
+// (node, bank, depth of the node) and the key gains context_weight * m(y), m = bank + depth.  An extension's thread takes its
+// context_step in phase A beside its ngram_token_logp - at the root, where most prefixes are, one probe of the edge table; only a
+// failing match reads node records - a stay proposal copies its state, and there is no new barrier.  The epilogue adds keep in
+// place of depth (ctx(y)) and writes out_ctx in final order.  Like lm(y), the state is a function of the label sequence alone, so
+// the identity rule carries over.  With CTX = false none of it is compiled.
+//
 // The limit on the beam, the fusion rule, the final ranking and the hash's finaliser are nbest.hpp's, shared with rescore.hip and
 // ngram.hip, so the list this kernel writes is ranked as they rank it; the checks of the LM arguments are ngram.hpp's ngram_args.
 #include "common.hpp"
 #include "nbest.hpp"
 #include "ngram.hpp"
+#include "context.hpp"
 
 namespace {
 
@@ -53,13 +61,14 @@ __device__ __forceinline__ float cb_lae(float a, float b) {
 // comes before nothing.
 __device__ __forceinline__ int cb_before(float kp, int ep, float k, int e) { return (kp > k || (kp == k && ep < e)) ? 1 : 0; }
 
-template <bool LM>
+template <bool LM, bool CTX>
 struct CbBeam {  // one of the two beams; slot = rank of the prefix (key descending)
   float pb[CB_MAX_K], pnb[CB_MAX_K], tot[CB_MAX_K];  // log-mass ending in blank / in non-blank, and their logaddexp
   uint64_t hash[CB_MAX_K], phash[CB_MAX_K];         // of the prefix, and of the prefix without its last token
   int len[CB_MAX_K], last[CB_MAX_K], node[CB_MAX_K];
   float lm[LM ? CB_MAX_K : 1];                      // LM only: lm(y), and the second and third newest tokens of (bos, y), -1 = none
   int t1[LM ? CB_MAX_K : 1], t2[LM ? CB_MAX_K : 1];
+  int cnode[CTX ? CB_MAX_K : 1], cbank[CTX ? CB_MAX_K : 1], cdep[CTX ? CB_MAX_K : 1];  // CTX only: context.hpp's state of the prefix
 };
 
 struct CbFuse {  // what the LM form takes besides the search's own arguments
@@ -67,23 +76,29 @@ struct CbFuse {  // what the LM form takes besides the search's own arguments
   int bos, eos;
   float lm_weight, length_bonus;
   float *out_ctc, *out_lm;
+  context_view ctx;  // what the CTX form takes on top (behind the LM form's: their offsets stay)
+  float ctx_weight;
+  int32_t* out_ctx;
 };
 
 // log p(w | (bos, y)) for the prefix y in slot i of the beam
-template <bool LM>
-__device__ __forceinline__ float cb_token_logp(const CbFuse& f, const CbBeam<LM>& g, int i, int w) {
+template <bool LM, bool CTX>
+__device__ __forceinline__ float cb_token_logp(const CbFuse& f, const CbBeam<LM, CTX>& g, int i, int w) {
   const int len = g.len[i];
   const int64_t c[NGRAM_MAX_CTX] = {len > 0 ? g.last[i] : f.bos, g.t1[i], g.t2[i]};
   return ngram_token_logp(f.lm, w, c, len + 1 < NGRAM_MAX_CTX ? len + 1 : NGRAM_MAX_CTX);
 }
 
-template <typename T, bool LM>
+template <typename T, bool LM, bool CTX>
 __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
     const T* __restrict__ x, const float* __restrict__ lse, const int64_t* __restrict__ cand_id, const float* __restrict__ cand_lp,
     const int64_t* __restrict__ in_len, int64_t* __restrict__ out_ids, int32_t* __restrict__ out_len, float* __restrict__ out_score,
     int2* __restrict__ nodes_all, int64_t Tmax, int64_t V, int K, int C, int n_best, int blank, int64_t pad,
     const int32_t* __restrict__ rowoff, const CbFuse fuse) {
-  __shared__ CbBeam<LM> beam[2];
+  static_assert(LM || !CTX, "the context form is built on the LM form");
+  __shared__ CbBeam<LM, CTX> beam[2];
+  __shared__ int s_enode[CTX ? CB_MAX_E : 1], s_ebank[CTX ? CB_MAX_E : 1], s_edep[CTX ? CB_MAX_E : 1];  // CTX only: every proposal's state
+  __shared__ int s_ctx[CTX ? CB_MAX_K : 1];             // CTX only: ctx(y) per beam slot
   __shared__ float s_elm[LM ? CB_MAX_E : 1];            // LM only: lm(y) of every proposal of the frame
   __shared__ int s_ord[LM ? CB_MAX_K : 1];              // LM only: beam slot of the k-th best by the final score
   __shared__ float s_fin[LM ? CB_MAX_K : 1], s_lmf[LM ? CB_MAX_K : 1];  // final score and lm(y) + p(eos | y) per beam slot
@@ -98,11 +113,12 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
   int2* nodes = nodes_all + (int64_t)b * (1 + (int64_t)K * Tmax);     // (parent node, token); node 0 = the empty prefix, never read
   const float nan = __int_as_float(0x7fc00000);
   if (tid == 0) {
-    CbBeam<LM>& g = beam[0];
+    CbBeam<LM, CTX>& g = beam[0];
     g.pb[0] = 0.f, g.pnb[0] = -INFINITY, g.tot[0] = 0.f;
     g.hash[0] = CB_ROOT_HASH, g.phash[0] = 0;
     g.len[0] = 0, g.last[0] = -1, g.node[0] = 0;
     if constexpr (LM) g.lm[0] = 0.f, g.t1[0] = -1, g.t2[0] = -1;
+    if constexpr (CTX) g.cnode[0] = 0, g.cbank[0] = 0, g.cdep[0] = 0;
   }
   int cur = 0, nbeam = 1;
   __syncthreads();
@@ -123,8 +139,8 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
     }
     __syncthreads();
     for (int tt = 0; tt < nt; ++tt) {  // (block-uniform bounds: nt)
-      const CbBeam<LM>& g = beam[cur];
-      CbBeam<LM>& gn = beam[cur ^ 1];
+      const CbBeam<LM, CTX>& g = beam[cur];
+      CbBeam<LM, CTX>& gn = beam[cur ^ 1];
       const int nlive = K + nbeam * C, npad = (nlive + 3) & ~3;  // proposals 0 .. K-1 stay, K + i C + s extends prefix i by slot s
       const float lpb = s_lpb[tt];
       // ---- phase A: the proposals
@@ -132,6 +148,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
         // LM: the extensions (at most 256) come first, one thread each, so that all their probes are in flight together
         const int e = !LM ? q : q < npad - K ? q + K : q - (npad - K);
         float npb = -INFINITY, npnb = -INFINITY, key = nan, elm = 0.f;
+        context_state cs{0, 0, 0};
         if (e < nbeam) {  // prefix e stays: blank, a repeat of its last label, and the extension of its parent that recreates it
           const int last = g.last[e], len = g.len[e];
           npb = g.tot[e] + lpb;
@@ -145,7 +162,12 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
               if (g.len[i] + 1 == len && g.hash[i] == ph) npnb = cb_lae(npnb, (g.last[i] == last ? g.pb[i] : g.tot[i]) + lp_rep);
           }
           key = cb_lae(npb, npnb);
-          if constexpr (LM) elm = g.lm[e], key = nbest_fuse(key, elm, len, fuse.lm_weight, fuse.length_bonus);
+          if constexpr (CTX) {  // a stay proposal copies its state
+            elm = g.lm[e], cs = context_state{g.cnode[e], g.cbank[e], g.cdep[e]};
+            key = nbest_fuse_ctx(key, elm, cs.bank + cs.depth, len, fuse.lm_weight, fuse.ctx_weight, fuse.length_bonus);
+          } else if constexpr (LM) {
+            elm = g.lm[e], key = nbest_fuse(key, elm, len, fuse.lm_weight, fuse.length_bonus);
+          }
         } else if (e >= K && e < nlive) {
           const int i = (e - K) / C, s = (e - K) - i * C;
           const int c = s_cid[tt][s];
@@ -163,15 +185,22 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
                 ok = elm > -INFINITY;  // an extension the LM forbids (-inf, or NaN) is not proposed
               }
             }
+            if constexpr (CTX) {  // m(y + c): the walk's step, beside the LM's probes; a weight of 0 reads no graph
+              if (ok && fuse.ctx_weight != 0.f) cs = context_step(fuse.ctx, context_state{g.cnode[i], g.cbank[i], g.cdep[i]}, c);
+            }
             if (ok) {
               npnb = base + s_clp[tt][s];
               key = npnb;
-              if constexpr (LM) key = nbest_fuse(key, elm, len1, fuse.lm_weight, fuse.length_bonus);
+              if constexpr (CTX)
+                key = nbest_fuse_ctx(key, elm, cs.bank + cs.depth, len1, fuse.lm_weight, fuse.ctx_weight, fuse.length_bonus);
+              else if constexpr (LM)
+                key = nbest_fuse(key, elm, len1, fuse.lm_weight, fuse.length_bonus);
             }
           }
         }
         s_key[e] = key, s_epb[e] = npb, s_epnb[e] = npnb;
         if constexpr (LM) s_elm[e] = elm;
+        if constexpr (CTX) s_enode[e] = cs.node, s_ebank[e] = cs.bank, s_edep[e] = cs.depth;
       }
       __syncthreads();
       // ---- phase B: rank by counting, the K first become the next beam
@@ -188,6 +217,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
         }
         if (k == k && rank < K) {
           gn.pb[rank] = s_epb[e], gn.pnb[rank] = s_epnb[e];
+          if constexpr (CTX) gn.cnode[rank] = s_enode[e], gn.cbank[rank] = s_ebank[e], gn.cdep[rank] = s_edep[e];
           if constexpr (LM) {  // the key is no longer the CTC total: an extension's is its pnb, a stay's is recomputed
             gn.tot[rank] = e < K ? cb_lae(s_epb[e], s_epnb[e]) : s_epnb[e];
             gn.lm[rank] = s_elm[e];
@@ -216,19 +246,28 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
   }
   // the beam is in score order already: its first n_best slots are the result; the barrier that closed the last frame made it, and
   // the nodes (workgroup scope), visible
-  const CbBeam<LM>& g = beam[cur];
+  const CbBeam<LM, CTX>& g = beam[cur];
   if constexpr (LM) {
     // the EOS term and the final score, lanes < nbeam of the first wave; ranked again by nbest.hpp's rule (equal finals keep the
     // beam's order, a NaN ranks as -inf); the back-trace below runs in that order
     if (tid < 64) {  // (wave-uniform)
       const bool have = tid < nbeam;
       float lmf = 0.f, fin = -INFINITY;
+      int ctxv = 0;  // CTX: ctx(y) - keep in place of depth: a partial match that never completed earns nothing
       if (have) {
         if (fuse.lm_weight != 0.f) lmf = g.lm[tid] + cb_token_logp(fuse, g, tid, fuse.eos);
-        fin = nbest_fuse(g.tot[tid], lmf, g.len[tid], fuse.lm_weight, fuse.length_bonus);
+        if constexpr (CTX) {
+          if (fuse.ctx_weight != 0.f) ctxv = context_final(fuse.ctx, context_state{g.cnode[tid], g.cbank[tid], g.cdep[tid]});
+          fin = nbest_fuse_ctx(g.tot[tid], lmf, ctxv, g.len[tid], fuse.lm_weight, fuse.ctx_weight, fuse.length_bonus);
+        } else {
+          fin = nbest_fuse(g.tot[tid], lmf, g.len[tid], fuse.lm_weight, fuse.length_bonus);
+        }
       }
       const int rank = nbest_rank(fin, tid, nbeam);  // (block-uniform nbeam)
       if (have) s_ord[rank] = tid, s_fin[tid] = fin, s_lmf[tid] = lmf;
+      if constexpr (CTX) {
+        if (have) s_ctx[tid] = ctxv;
+      }
     }
     __syncthreads();
   }
@@ -244,6 +283,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
       out_score[(int64_t)b * n_best + tid] = have ? s_fin[from] : -INFINITY;
       fuse.out_ctc[(int64_t)b * n_best + tid] = have ? g.tot[from] : -INFINITY;
       fuse.out_lm[(int64_t)b * n_best + tid] = have ? s_lmf[from] : -INFINITY;
+      if constexpr (CTX) fuse.out_ctx[(int64_t)b * n_best + tid] = have ? s_ctx[from] : 0;
     } else {
       out_score[(int64_t)b * n_best + tid] = have ? g.tot[tid] : -INFINITY;
     }
@@ -260,7 +300,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_beam_kernel(
 }
 
 // the checks the two entry points share, and the launch; `who` names the entry point in the messages
-template <bool LM>
+template <bool LM, bool CTX>
 int cb_launch(const char* who, const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
               const int64_t* in_len, int64_t* out_ids, int32_t* out_len, float* out_score, void* workspace, int64_t B, int64_t T_, int64_t V,
               int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank, int64_t pad, const int32_t* row_offsets, const CbFuse& fuse,
@@ -274,11 +314,11 @@ int cb_launch(const char* who, const void* logits, int dt, const float* lse, con
   JS2T_CHECK(blank >= 0 && blank < V, "%s: blank %lld outside the vocabulary", who, (long long)blank);
   JS2T_CHECK(dt == JS2T_F32 || dt == JS2T_BF16, "bad dtype %d", dt);
   if (dt == JS2T_F32)
-    hipLaunchKernelGGL((ctc_beam_kernel<float, LM>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const float*)logits, lse,
+    hipLaunchKernelGGL((ctc_beam_kernel<float, LM, CTX>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const float*)logits, lse,
                        cand_id, cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand, (int)n_best,
                        (int)blank, pad, row_offsets, fuse);
   else
-    hipLaunchKernelGGL((ctc_beam_kernel<uint16_t, LM>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const uint16_t*)logits,
+    hipLaunchKernelGGL((ctc_beam_kernel<uint16_t, LM, CTX>), dim3((unsigned)B), dim3(CB_THREADS), 0, (hipStream_t)stream, (const uint16_t*)logits,
                        lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, (int2*)workspace, T_, V, (int)beam, (int)n_cand,
                        (int)n_best, (int)blank, pad, row_offsets, fuse);
   JS2T_LAUNCH_CHECK();
@@ -299,7 +339,7 @@ extern "C" int js2t_ctc_beam_search(const void* logits, int dt, const float* lse
                                     int64_t B, int64_t T_, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank,
                                     int64_t pad, const int32_t* row_offsets, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
-  return cb_launch<false>("ctc_beam_search", logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam,
+  return cb_launch<false, false>("ctc_beam_search", logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam,
                           n_cand, n_best, blank, pad, row_offsets, CbFuse{}, stream);
 }
 
@@ -312,10 +352,31 @@ extern "C" int js2t_ctc_beam_search_lm(const void* logits, int dt, const float* 
   if (B == 0) return JS2T_OK;
   const char* who = "ctc_beam_search_lm";
   JS2T_CHECK(out_ctc && out_lm, "%s: null pointer (out_ctc / out_lm)", who);
-  CbFuse fuse;
+  CbFuse fuse{};
   if (const int rc = ngram_args(who, uni, table, capacity, max_probe, lm_order, V, bos, eos, lm_weight, length_bonus, &fuse.lm)) return rc;
   fuse.bos = (int)bos, fuse.eos = (int)eos, fuse.lm_weight = lm_weight, fuse.length_bonus = length_bonus;
   fuse.out_ctc = out_ctc, fuse.out_lm = out_lm;
-  return cb_launch<true>(who, logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam, n_cand, n_best,
+  return cb_launch<true, false>(who, logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam, n_cand, n_best,
                          blank, pad, row_offsets, fuse, stream);
+}
+
+extern "C" int js2t_ctc_beam_search_ctx(const void* logits, int dt, const float* lse, const int64_t* cand_id, const float* cand_lp,
+                                        const int64_t* in_len, const float* uni, const void* table, int64_t capacity, int32_t max_probe,
+                                        int32_t lm_order, const void* ctx_nodes, const void* ctx_edges, int64_t ctx_capacity,
+                                        int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail, int64_t* out_ids, int32_t* out_len,
+                                        float* out_score, float* out_ctc, float* out_lm, int32_t* out_ctx, void* workspace, int64_t B,
+                                        int64_t T_, int64_t V, int32_t beam, int32_t n_cand, int32_t n_best, int64_t blank, int64_t pad,
+                                        int64_t bos, int64_t eos, float lm_weight, float context_weight, float length_bonus,
+                                        const int32_t* row_offsets, js2t_stream stream) {
+  if (B == 0) return JS2T_OK;
+  const char* who = "ctc_beam_search_ctx";
+  JS2T_CHECK(out_ctc && out_lm && out_ctx, "%s: null pointer (out_ctc / out_lm / out_ctx)", who);
+  CbFuse fuse{};
+  if (const int rc = ngram_args(who, uni, table, capacity, max_probe, lm_order, V, bos, eos, lm_weight, length_bonus, &fuse.lm)) return rc;
+  if (const int rc = context_args(who, ctx_nodes, ctx_edges, ctx_capacity, ctx_max_probe, ctx_n_nodes, ctx_max_fail, V, context_weight, &fuse.ctx))
+    return rc;
+  fuse.bos = (int)bos, fuse.eos = (int)eos, fuse.lm_weight = lm_weight, fuse.length_bonus = length_bonus;
+  fuse.out_ctc = out_ctc, fuse.out_lm = out_lm, fuse.ctx_weight = context_weight, fuse.out_ctx = out_ctx;
+  return cb_launch<true, true>(who, logits, dt, lse, cand_id, cand_lp, in_len, out_ids, out_len, out_score, workspace, B, T_, V, beam, n_cand,
+                               n_best, blank, pad, row_offsets, fuse, stream);
 }

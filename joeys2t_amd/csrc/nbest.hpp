@@ -1,6 +1,6 @@
-// The rules the n-best entry points share (EXTENSION; the reference has no n-best list): js2t_ctc_beam_search(_lm) writes the list,
-// js2t_rescore, js2t_ngram_rescore and js2t_mbr_rescore re-rank it, and they compose because each of these rules exists once, here.
-// The semantics are stated in the header; rescore.hip, ngram.hip, ctc_beam.hip and mbr.hip are the files that apply them.
+// The rules the n-best entry points share (EXTENSION; the reference has no n-best list): js2t_ctc_beam_search(_lm, _ctx) writes the list,
+// js2t_rescore, js2t_ngram_rescore, js2t_context_rescore and js2t_mbr_rescore re-rank it, and they compose because each of these rules exists once, here.
+// The semantics are stated in the header; rescore.hip, ngram.hip, context.hip, ctc_beam.hip and mbr.hip are the files that apply them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +30,19 @@ __device__ __forceinline__ float nbest_fuse(float base, float lm, int len, float
 #pragma clang fp contract(off)
   float s = base;
   if (lm_weight != 0.f) s += lm_weight * lm;
+  if (length_bonus != 0.f) s += length_bonus * (float)len;
+  return s;
+}
+
+// nbest_fuse with the context term (js2t_ctc_beam_search_ctx, js2t_context_rescore): base + lm_weight * lm + context_weight *
+// (float)count + length_bonus * len under the same rules - and with context_weight == 0 it is nbest_fuse, bit for bit.  The count is
+// an integer: exact in f32 whatever the order it was summed in.
+__device__ __forceinline__ float nbest_fuse_ctx(float base, float lm, int count, int len, float lm_weight, float context_weight,
+                                                float length_bonus) {
+#pragma clang fp contract(off)
+  float s = base;
+  if (lm_weight != 0.f) s += lm_weight * lm;
+  if (context_weight != 0.f) s += context_weight * (float)count;
   if (length_bonus != 0.f) s += length_bonus * (float)len;
   return s;
 }

@@ -54,7 +54,18 @@ inline int ngram_args(const char* who, const float* uni, const void* table, int6
   return JS2T_OK;
 }
 
-__device__ __forceinline__ uint64_t ngram_entry_key(const uint4 e) { return (uint64_t)e.x | ((uint64_t)e.y << 32); }
+__host__ __device__ __forceinline__ uint64_t ngram_entry_key(const uint4 e) { return (uint64_t)e.x | ((uint64_t)e.y << 32); }
+
+// the probing rule alone, for any table of this entry format (the LM's, and context.hpp's edge table): `e` holds the first probe
+// (slot `home`) and, on return, the last entry examined; only a probe that met another key walks on, at most max_probe slots in all
+__host__ __device__ __forceinline__ bool ngram_probe(const uint4* table, uint64_t mask, int max_probe, uint64_t key, uint64_t home, uint4& e) {
+  uint64_t k = ngram_entry_key(e);
+  for (int i = 1; key != 0 && k != key && k != 0 && i < max_probe; ++i) {
+    e = table[(home + (uint64_t)i) & mask];
+    k = ngram_entry_key(e);
+  }
+  return key != 0 && k == key;
+}
 
 struct ngram_hit {
   bool found;
@@ -66,13 +77,9 @@ __device__ __forceinline__ uint64_t ngram_home(const ngram_view& lm, uint64_t ke
 
 // the rest of a lookup whose first probe `e` (slot `home`) has been loaded; only a probe that met another key walks on
 __device__ __forceinline__ ngram_hit ngram_resolve(const ngram_view& lm, uint64_t key, uint64_t home, uint4 e) {
-  uint64_t k = ngram_entry_key(e);
-  for (int i = 1; key != 0 && k != key && k != 0 && i < lm.max_probe; ++i) {
-    e = lm.table[(home + (uint64_t)i) & lm.mask];
-    k = ngram_entry_key(e);
-  }
   ngram_hit h;
-  h.found = key != 0 && k == key, h.logp = __uint_as_float(e.z), h.backoff = __uint_as_float(e.w);
+  h.found = ngram_probe(lm.table, lm.mask, lm.max_probe, key, home, e);
+  h.logp = __uint_as_float(e.z), h.backoff = __uint_as_float(e.w);
   return h;
 }
 

@@ -886,6 +886,70 @@ def ctc_beam_search_lm(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_bes
     return ids, n, score, ctc, lms
 
 
+def _context_args(who, context, context_weight, dev, on, V):
+    """The graph arguments of js2t_ctc_beam_search_ctx and js2t_context_rescore from a biasing.ContextGraph, or from None, which
+    stands for context_weight 0: (nodes, edges, capacity, max_probe, n_nodes, max_fail).  V: the width the graph must be over, or
+    None to take the graph's."""
+    if context is None:
+        if float(context_weight) != 0.0:
+            raise Js2tError(f"{who}: without a context graph, context_weight 0 expected")
+        return None, None, 0, 1, 0, 0
+    if context.nodes_dev is None or context.nodes_dev.device != dev:
+        raise Js2tError(f"{who}: the context graph is on {context.device}, the {on} on {dev}: context.to(device) first")
+    if V is not None and int(V) != context.V:
+        raise Js2tError(f"{who}: the context graph is over {context.V} ids, the {on} over {V}")
+    return context.nodes_dev, context.edges_dev, context.capacity, context.max_probe, context.n_nodes, context.max_fail
+
+
+def ctc_beam_search_ctx(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_best: int, blank: int, pad: int, lm, bos: int, eos: int,
+                        lm_weight: float, length_bonus: float, context, context_weight: float, pack: "PackedRows" = None, workspace=None):
+    """CTC prefix beam search with contextual biasing inside the beam (js2t_ctc_beam_search_ctx): ctc_beam_search_lm's arguments;
+    context: a joeys2t_amd.biasing.ContextGraph over the V ids of the logits on their device, or None when context_weight is 0.
+    Every frame prunes by ctc + lm_weight * lm + context_weight * m + length_bonus * length, m = the tokens of the prefix that lie in
+    completed phrases or in the partial match at its end; the final score counts completed phrases only.  Biasing adds no
+    candidates: a phrase token that is not among a frame's candidates (<= 8) is still not proposed.  Returns ctc_beam_search_lm's
+    five tensors and context i32 [B, n_best]: the matched tokens of every returned labelling (0 without a graph)."""
+    who = "ctc_beam_search_ctx"
+    B, T, V, roff, in_len, workspace, ids, n, score = _beam_args(who, logits3d, lse, cand_id, cand_lp, in_len, beam, n_best, pack, workspace)
+    uni, table, capacity, max_probe, order_lm, _ = _lm_args(who, lm, lm_weight, logits3d.device, "logits", V)
+    nodes, edges, ccap, cprobe, n_nodes, max_fail = _context_args(who, context, context_weight, logits3d.device, "logits", V)
+    ctc, lms = torch.empty_like(score), torch.empty_like(score)
+    ctx = torch.empty_like(n)
+    check(lib().js2t_ctc_beam_search_ctx(_p(logits3d), dt_code(logits3d), _p(lse), _p(cand_id), _p(cand_lp), _p(in_len), _p(uni), _p(table),
+                                         capacity, max_probe, order_lm, _p(nodes), _p(edges), ccap, cprobe, n_nodes, max_fail, _p(ids), _p(n),
+                                         _p(score), _p(ctc), _p(lms), _p(ctx), _p(workspace), B, T, V, beam, cand_id.shape[1], n_best, blank,
+                                         pad, int(bos), int(eos), float(lm_weight), float(context_weight), float(length_bonus), roff,
+                                         _stream()), "js2t_ctc_beam_search_ctx")
+    return ids, n, score, ctc, lms, ctx
+
+
+def context_rescore(ids, n, base_score, N: int, context, context_weight: float, Lp: int = None, out=None):
+    """The contextual-biasing count of an n-best list (js2t_context_rescore): ids i64 [B, N, T] or [R, T], n i32 [B, N] or [R],
+    base_score f32 [B, N] or [R] the last stage's score; context: a joeys2t_amd.biasing.ContextGraph on the tensors' device, or None
+    when context_weight is 0.  Lp bounds the lengths (a slot with n > Lp - 1 is dead); default T + 1 - no host read is needed.
+    Returns (ctx i32 [R]: the tokens of every hypothesis that lie in completed phrases; score f32 [R] = base_score + context_weight *
+    ctx, a weight of 0 left out, both in input slot order; order i32 [B, N]: the input slot of every utterance's k-th best).  Dead
+    slots (base_score -inf, n outside 0 .. Lp - 1): ctx 0, score -inf, ranked last.  It re-ranks what the list holds: a phrase the
+    first pass pruned is not brought back - that is what ctc_beam_search_ctx is for.
+    out: (ctx, score, order) to write instead of fresh ones, contiguous."""
+    _dev(ids, n, base_score, *(out or ()))
+    N = int(N)
+    R, B = _nbest_args("context_rescore", ids, n, base_score, N, "scores")
+    T = ids.shape[-1]
+    Lp = T + 1 if Lp is None else int(Lp)
+    nodes, edges, ccap, cprobe, n_nodes, max_fail = _context_args("context_rescore", context, context_weight, ids.device, "hypotheses", None)
+    want = (((R, ), torch.int32), ((R, ), torch.float32), ((B, N), torch.int32))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=ids.device) for s, d in want)
+    elif len(out) != 3 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
+        raise Js2tError(f"context_rescore: out = contiguous (i32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
+    ctx, score, order = out
+    check(lib().js2t_context_rescore(_p(ids), T, _p(n), _p(base_score), _p(nodes), _p(edges), ccap, cprobe, n_nodes, max_fail, _p(ctx),
+                                     _p(score), _p(order), B, N, Lp, context.V if context is not None else 1, float(context_weight),
+                                     _stream()), "js2t_context_rescore")
+    return ctx, score, order
+
+
 def _nbest_args(who, ids, n, score, N, scores, R=None):
     """The checks of an n-best list - ids i64 [B, N, T] or [R, T], n i32 and score f32 of R = B * N hypotheses - for the two entry
     points that re-rank one.  R: the count the caller's logits fix; None: the list itself says it.  Returns (R, B); `who` names the

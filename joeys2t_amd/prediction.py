@@ -20,7 +20,7 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import _decision_args, ctc_attention_rescore, ctc_beam_search, search
+from joeys2t_amd.search import _context_args, _decision_args, ctc_attention_rescore, ctc_beam_search, search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
@@ -28,7 +28,8 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
             decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
-            length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0):
+            length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0, context=None,
+            context_weight: float = 0.0):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -48,7 +49,11 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     decoder instead (shallow fusion, `search.ctc_beam_search`); the attention decoder refuses it too.
     decision="mbr" / mbr_scale (EXTENSION; default "map"): the two CTC decoders rank their n-best list by minimum Bayes risk - the
     smallest expected edit distance to the list under the softmax of mbr_scale * score - instead of by score (`search.ctc_beam_search`);
-    the hypotheses of a sentence then come in ascending risk, each with its model score.  The attention decoder refuses them."""
+    the hypotheses of a sentence then come in ascending risk, each with its model score.  The attention decoder refuses them.
+    context / context_weight (EXTENSION): contextual biasing - a joeys2t_amd.biasing.ContextGraph of phrases that matter for these
+    batches and the boost per matched token, applied inside the CTC beam of either CTC decoder (`search.ctc_beam_search`); a phrase
+    token outside a frame's `ctc_candidates` best labels is still not proposed.  The attention decoder refuses them; a weight that is
+    not finite, or non-zero without a graph, is refused before a model is touched."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
     if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
@@ -59,6 +64,9 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     if decoder == "attention" and lm_fusion != "rescore":
         raise ValueError("predict: lm_fusion applies to the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
     mbr, mbr_scale = _decision_args("predict", decision, mbr_scale)
+    biased, context_weight = _context_args("predict", context, context_weight)
+    if decoder == "attention" and (context is not None or biased):
+        raise ValueError("predict: context / context_weight bias the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
     if decoder == "attention" and mbr:
         raise ValueError("predict: decision='mbr' ranks the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
                          "no such list")
@@ -68,6 +76,8 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         lm_kw = dict(lm_kw, lm_fusion=lm_fusion)  # (without an lm or a bonus the decoder refuses it)
     if mbr:
         lm_kw = dict(lm_kw, decision="mbr", mbr_scale=mbr_scale)
+    if biased:
+        lm_kw = dict(lm_kw, context=context, context_weight=context_weight)
     ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}

@@ -515,6 +515,16 @@ def _lm_fusion_arg(who, lm_fusion, rerank):
     return lm_fusion == "search"
 
 
+def _context_args(who, context, context_weight):
+    """(bias at all?, context_weight) of the contextual-biasing options of the two CTC decoders; refused before the model is touched"""
+    context_weight = float(context_weight)
+    if not math.isfinite(context_weight):
+        raise ValueError(f"{who}: context_weight {context_weight} not finite")
+    if context is None and context_weight != 0.0:
+        raise ValueError(f"{who}: context_weight {context_weight} without a context graph")
+    return context is not None and context_weight != 0.0, context_weight
+
+
 def _decision_args(who, decision, mbr_scale):
     """(rank by minimum Bayes risk?, mbr_scale) of the decision options of the two CTC decoders; refused before the model is touched"""
     if decision not in ("map", "mbr"):
@@ -534,24 +544,35 @@ def _map_rank(order, B, N, dev):
     return slots if order is None else torch.empty((B, N), dtype=torch.int64, device=dev).scatter_(1, order.to(torch.int64), slots)
 
 
-def _ctc_first_pass(model, batch, who, beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=False):
+def _ctc_first_pass(model, batch, who, beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=False, context=None,
+                    context_weight=0.0):
     """The first pass of the two CTC decoders (inside their no_grad): encode once, project, pick the candidates of every frame and
     search for the N best prefixes (blank = BOS) - `fused`: with the LM in the beam (ops.ctc_beam_search_lm over the model's
-    vocabulary, the lm moved to the device if need be).  Returns (ids i64 [B, N, T], n i32 [B, N], ctc f32 [B, N] the pure CTC score,
-    score f32 [B, N] the search's own: ctc itself unless fused, (B, T, V), [encoder output, its mask] with want_encoder)."""
+    vocabulary, the lm moved to the device if need be); with a `context` graph: always ops.ctc_beam_search_ctx, the LM taking part
+    in it only when fused.  Returns (ids i64 [B, N, T], n i32 [B, N], ctc f32 [B, N] the pure CTC score, score f32 [B, N] the
+    search's own: ctc itself unless fused or biased, (B, T, V), [encoder output, its mask] with want_encoder, the context counts
+    i32 [B, N] or None without a graph)."""
     from joeys2t_amd.alignment import _ctc_frames
     ctc_out, _, in_len, *enc = _ctc_frames(model, batch, who=who, want_lse=False, want_encoder=want_encoder)
     B, T, V = ctc_out.shape
     logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
     cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-    if not fused:
+    if not fused and context is None:
         ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
-        return ids, n, ctc, ctc, (B, T, V), enc
-    if lm is not None and lm.device != logits.device:
+        return ids, n, ctc, ctc, (B, T, V), enc, None
+    if fused and lm is not None and lm.device != logits.device:
         lm.to(logits.device)
-    ids, n, score, ctc, _ = ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm,
-                                                   model.bos_index, model.eos_index, lm_weight, length_bonus)
-    return ids, n, ctc, score, (B, T, V), enc
+    if context is None:
+        ids, n, score, ctc, _ = ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm,
+                                                       model.bos_index, model.eos_index, lm_weight, length_bonus)
+        return ids, n, ctc, score, (B, T, V), enc, None
+    if context.device != logits.device:
+        context.to(logits.device)
+    in_beam = (lm, lm_weight, length_bonus) if fused else (None, 0.0, 0.0)  # lm_fusion="rescore": the LM stays behind the search
+    ids, n, score, ctc, _, ctx = ops.ctc_beam_search_ctx(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index,
+                                                         in_beam[0], model.bos_index, model.eos_index, in_beam[1], in_beam[2], context,
+                                                         context_weight)
+    return ids, n, ctc, score, (B, T, V), enc, ctx
 
 
 def _first_rows(order, n_best, N):
@@ -571,7 +592,7 @@ def _nbest_numpy(ids, n, score):
 
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
                     length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore", decision: str = "map",
-                    mbr_scale: float = 1.0, return_parts: bool = False):
+                    mbr_scale: float = 1.0, return_parts: bool = False, context=None, context_weight: float = 0.0):
     """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
     `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
     `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
@@ -594,8 +615,17 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     the row would carry with decision="map".  Still no host read before the final copy.  A hypothesis of more than
     ops.edit_max_len() labels takes no part (it is ranked last).
     return_parts: a fourth element, a dict of per-returned-row NumPy data: "map_rank" i64 [B * n_best] (the row's rank within its
-    utterance by the model score) and, with decision="mbr", "risk" and "posterior" f32 [B * n_best]."""
+    utterance by the model score) and, with decision="mbr", "risk" and "posterior" f32 [B * n_best].
+    context / context_weight (contextual biasing: a joeys2t_amd.biasing.ContextGraph of phrases that matter for this batch, and the
+    boost per matched token): with a graph and a non-zero weight the search is js2t_ctc_beam_search_ctx - every frame prunes by
+    ctc + context_weight * m, m = the tokens of the prefix inside completed phrases or the partial match at its end, and the final
+    score counts completed phrases only.  Biasing acts inside the beam, always: there is no "rescore" mode for it.  The LM and the
+    bonus take part in that kernel only under lm_fusion="search"; under "rescore" they re-rank the biased list, the kernel's final
+    score being the base of the n-gram stage.  Biasing adds no candidates: a phrase token that is not among a frame's `candidates`
+    (<= 8) best labels is still not proposed.  return_parts gains "context" i32 [B * n_best], the matched tokens of every row.  A
+    weight that is not finite, or non-zero without a graph, is refused before the model is touched."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
+    biased, context_weight = _context_args("ctc_beam_search", context, context_weight)
     fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
     mbr, mbr_scale = _decision_args("ctc_beam_search", decision, mbr_scale)
     if not 1 <= n_best <= beam_size:
@@ -612,11 +642,13 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     beam_size, n_best = int(beam_size), int(n_best)
     N = n_rescore if mbr or (rerank and not fused) else n_best  # the slots searched for
     with torch.no_grad():
-        ids, n, ctc, score, (B, T, _), _ = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
-                                                           length_bonus)
+        ids, n, ctc, score, (B, T, _), _, ctx = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
+                                                                length_bonus, context=context if biased else None,
+                                                                context_weight=context_weight)
         order = None  # (the search returns its list best first)
         if rerank and not fused:  # the N best re-ranked by the n-gram LM and the length bonus, the n_best first of them returned
-            _, _, score, order = _ngram_rerank(model, ids, n, ctc, N, lm, lm_weight, length_bonus, ids.device)  # Lp = T + 1: no length to read
+            # the base is the search's own score: the CTC score, with the context term when the search was biased; Lp = T + 1: no length to read
+            _, _, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, ids.device)
         map_rank = _map_rank(order, B, N, ids.device) if return_parts else None
         if mbr:  # the list ranked by its expected edit distance instead; Lp from the table's width: no length to read
             _, posterior, risk, order = ops.mbr_rescore(ids, n, score.reshape(B * N), N, mbr_scale, Lp=min(T, ops.edit_max_len()) + 1)
@@ -628,12 +660,15 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
         parts = {"map_rank": (map_rank.reshape(B * N)[rows] if order is not None else map_rank.reshape(B * N)).cpu().numpy()}
         if mbr:
             parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
+        if biased:
+            parts["context"] = (ctx.reshape(B * N)[rows] if order is not None else ctx.reshape(B * N)).cpu().numpy()
     return (*_nbest_numpy(ids, n, score), parts)
 
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
                           n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
-                          length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0):
+                          length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0,
+                          context=None, context_weight: float = 0.0):
     """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
     of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
     over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
@@ -656,8 +691,15 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     device by their expected edit distance to the list under the posterior softmax(mbr_scale * final score) (js2t_mbr_rescore); the
     n_best first are returned.  The rows of an utterance are then in ASCENDING RISK, not in descending score; the scores column keeps
     each row's final model score.  The parts gain "risk" and "posterior" f32 [B * n_best] and "map_rank" i64 [B * n_best], the row's
-    rank within its utterance by the final model score.  The host read that sizes the decoder pass stays the only one."""
+    rank within its utterance by the final model score.  The host read that sizes the decoder pass stays the only one.
+    context / context_weight (contextual biasing, `ctc_beam_search`): with a graph and a non-zero weight the first pass is the biased
+    search (js2t_ctc_beam_search_ctx with n_best = n_rescore; the LM in it only under lm_fusion="search"), so the list that is
+    re-scored holds the labellings the phrases keep alive.  js2t_rescore takes the pure CTC score as ever; the context term,
+    context_weight * the matched tokens of completed phrases, is added behind the n-gram stage and in front of the MBR decision
+    (js2t_context_rescore), and its ranking decides.  The parts gain "context" i32 [B * n_best].  A weight that is not finite, or
+    non-zero without a graph, is refused before the model is touched."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
+    biased, context_weight = _context_args("ctc_attention_rescore", context, context_weight)
     fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
     mbr, mbr_scale = _decision_args("ctc_attention_rescore", decision, mbr_scale)
     n_rescore = beam_size if n_rescore is None else n_rescore
@@ -669,8 +711,9 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         raise ValueError(f"ctc_attention_rescore: ctc_weight {ctc_weight} outside [0, 1]")
     N = n_rescore
     with torch.no_grad():
-        ids, n, ctc, _, (B, T, _), (encoder_output, src_mask) = _ctc_first_pass(model, batch, "ctc_attention_rescore", beam_size, N, candidates,
-                                                                                fused, lm, lm_weight, length_bonus, want_encoder=True)
+        ids, n, ctc, _, (B, T, _), (encoder_output, src_mask), _ = _ctc_first_pass(
+            model, batch, "ctc_attention_rescore", beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=True,
+            context=context if biased else None, context_weight=context_weight)
         dev = ids.device
         Lp = int(n.max().item()) + 1 if n.numel() else 1  # the one host read: it sizes the decoder pass
         ids2 = ids.view(B * N, T)
@@ -683,6 +726,8 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         if rerank:
             lm_tok, lm_score, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, dev, Lp=Lp,
                                                            want_tokens=return_parts)
+        if biased:  # the context term on top of whatever the stages before it made of the list
+            ctx, score, order = ops.context_rescore(ids, n, score, N, context, context_weight, Lp=Lp)
         if mbr:  # the same list and scores, ranked by the expected edit distance instead
             map_rank = _map_rank(order, B, N, dev) if return_parts else None
             _, posterior, risk, order = ops.mbr_rescore(ids, n, score, N, mbr_scale, Lp=Lp)
@@ -701,4 +746,6 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
         if mbr:
             parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
             parts["map_rank"] = map_rank.reshape(B * N)[rows].cpu().numpy()
+        if biased:
+            parts["context"] = ctx[rows].cpu().numpy()
     return out_ids, out_score, out_n, parts
