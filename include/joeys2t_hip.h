@@ -690,6 +690,42 @@ int js2t_edit_distance(const int64_t* a, int64_t a_stride, const int32_t* a_len,
 int js2t_mbr_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* score, int32_t* dist, float* posterior,
                      float* risk, int32_t* order, int64_t B, int32_t N, int64_t Lp, float scale, js2t_stream stream);
 
+/* EXTENSION (the reference has no n-best list): token confidence from an n-best list - for every token of a chosen hypothesis, the
+ * posterior mass of the list entries that agree with it there.  It says how much of the LIST's mass agrees with a token, nothing
+ * more.  It takes js2t_mbr_rescore's layout and composes with the same stages: R = B * N hypotheses, N <= 32 slots per utterance;
+ * the labels of hypothesis r at ids + r * ids_stride; n i32 [R] label counts; score f32 [R] the last stage's score.
+ * Dead slots: js2t_mbr_rescore's rule (score = -inf, n < 0 or n > Lp - 1, a score that is NaN or +inf).  Ids behind n[r] and all ids
+ * of a dead slot are never read.  Ids are compared as full 64-bit values (5 and 2^40 + 5 differ).
+ * pivot i32 [B, P], 1 <= P <= N: the slots whose tokens get a confidence (a decoder passes the rows it returns).  A pivot outside
+ * 0 .. N-1, or one that names a dead slot, is a DEAD PIVOT: its conf, hyp_conf and match are exactly 0 and nothing of it is read.  (A
+ * pivot is device data: it cannot be refused on the host.)
+ * posterior f32 [R]: exactly js2t_mbr_rescore's rule and exactly its bits - z_k = scale * score_k rounded to f32, m = the maximum
+ * of z, e_k = exp(z_k - m) (exactly 1 where z_k = m), S = the sum of e_k in ascending slot order, p_k = e_k / S; 0 for a dead slot.
+ * The alignment of a pivot a (m labels) with a slot b (k labels): D is the unit-cost Levenshtein table with D[x][0] = x and
+ * D[0][y] = y; the path is traced back from (m, k) and takes at (x, y) the FIRST of these that applies:
+ *   1. x > 0, y > 0, a[x-1] == b[y-1] and D[x][y] == D[x-1][y-1]: a match - pivot position x-1 is MATCHED - go to (x-1, y-1);
+ *   2. x > 0, y > 0 and D[x][y] == D[x-1][y-1] + 1: a substitution, go to (x-1, y-1);
+ *   3. x > 0 and D[x][y] == D[x-1][y] + 1: the pivot's label is unmatched, go to (x-1, y);
+ *   4. otherwise go to (x, y-1).
+ * The roles are not symmetric: the pivot is always a ([0, 1, 0] gets [1, 1, 0] as the pivot of [1, 0, 1] and [0, 1, 1] as its other
+ * row), and a common prefix may not be trimmed ([0, 0] against [0] gives [0, 1]); a common suffix may.
+ * match u8 [B, P, N, Lp - 1] (optional, may be NULL): match[b, p, j, l] = 1 where position l of pivot p is matched by slot j, 0
+ * elsewhere and behind the pivot's length; for j == the pivot itself all ones inside its length, without a DP; all zeros for a dead j.
+ * conf f32 [B, P, Lp - 1]: conf[b, p, l] = the sum over live j, in ascending j, of p_j * (float)match[b, p, j, l], each product
+ * rounded to f32 before it is added (no contraction): one fixed order, the same bits alone and in a batch, on every run, under graph
+ * replay and with or without `match`.  Exactly 0 for l >= the pivot's length.
+ * hyp_conf f32 [B, P]: the posterior of the pivot's slot, the utterance-level figure.
+ * workspace: at least js2t_nbest_confidence_workspace(B, P, N, Lp) bytes of device memory, 4-byte aligned, contents irrelevant: the
+ * match masks and the 2-bit back-trace codes of every pair's table, about B * P * N * (Lp^2 / 4 + Lp / 8) bytes; the size function
+ * returns -1 for a shape the entry point refuses.
+ * Limits, all checked before anything is launched: 1 <= P <= N <= 32, Lp >= 1, Lp - 1 <= JS2T_EDIT_MAX_LEN, ids_stride >= Lp - 1,
+ * scale finite and > 0, B * N * N < 2^31, workspace_bytes at least the size function's; B = 0 returns 0.
+ * Two launches on `stream`; no atomics, no allocation, no synchronisation: capturable. */
+int64_t js2t_nbest_confidence_workspace(int64_t B, int32_t P, int32_t N, int64_t Lp);
+int js2t_nbest_confidence(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* score, const int32_t* pivot,
+                          float* posterior, float* conf, float* hyp_conf, uint8_t* match, void* workspace, int64_t workspace_bytes,
+                          int64_t B, int32_t N, int32_t P, int64_t Lp, float scale, js2t_stream stream);
+
 /* Single-query attention for KV-cached decoding (replaces the per-step full-prefix decoder pass of search.py:518-534 and
  * the per-step re-projection of the encoder states, transformer_layers.py:75-107 under beam search):
  * out[r, h*dh:(h+1)*dh] = softmax_j( (q[r,h]/sqrt(dh)) . K[row(r,j), j, h] ) V[row(r,j), j, h],  j < len.

@@ -11,16 +11,15 @@
 //        ascending slot order), the risk (ascending j, no contraction) and the rank by nbest.hpp's rule on the key -risk.
 //
 // The dead-slot rule of the list, the ranking and the limit on N are nbest.hpp's, shared with rescore.hip, ngram.hip and
-// ctc_beam.hip; a score that is no log mass (NaN, +inf) makes a slot dead here as well.
+// ctc_beam.hip; a score that is no log mass (NaN, +inf) makes a slot dead here as well (posterior.hpp, shared with confidence.hip).
 //
 // No atomics, no allocation, no workspace beyond `dist`, no host synchronisation: bit-reproducible, capturable.
 #include "common.hpp"
 #include "nbest.hpp"
+#include "posterior.hpp"
 #include "editdist.hpp"
 
 namespace {
-
-__device__ __forceinline__ bool mbr_dead(float score, int n, int64_t Lp) { return nbest_dead(score, n, Lp) || score != score || score == INFINITY; }
 
 __global__ __launch_bounds__(256) void edit_rows_kernel(const int64_t* __restrict__ a, int64_t a_stride, const int32_t* __restrict__ a_len,
                                                         const int64_t* __restrict__ b, int64_t b_stride, const int32_t* __restrict__ b_len,
@@ -68,12 +67,7 @@ __global__ __launch_bounds__(64) void mbr_risk_kernel(const int32_t* __restrict_
   const float sc = k < N ? score[r] : -INFINITY;
   const bool live = k < N && !mbr_dead(sc, n[r], Lp);
   const unsigned long long live_mask = __ballot(live);
-  const float z = live ? scale * sc : -INFINITY;
-  const float m = wave_max(z);
-  const float e = live ? (z == m ? 1.f : expf(z - m)) : 0.f;
-  float S = 0.f;
-  for (int j = 0; j < N; ++j) S += __shfl(e, j, 64);  // ascending slot order (a dead slot adds an exact 0)
-  const float pk = live ? e / S : 0.f;
+  const float pk = nbest_posterior(sc, live, N, scale);  // (posterior.hpp: the one statement of it)
   float rk = live ? 0.f : INFINITY;
   for (int j = 0; j < N; ++j) {  // (wave-uniform bounds)
     const float pj = __shfl(pk, j, 64);

@@ -1094,6 +1094,43 @@ def mbr_rescore(ids, n, score, N: int, scale: float = 1.0, Lp: int = None, out=N
     return dist, posterior, risk, order
 
 
+CONFIDENCE_MAX_WORKSPACE = 1 << 31  # bytes: a larger one is refused, never cut
+
+
+def nbest_confidence(ids, n, score, N: int, pivot, scale: float = 1.0, Lp: int = None, want_match: bool = False):
+    """Token confidence from an n-best list (js2t_nbest_confidence): ids i64 [B, N, T] or [R, T] (ctc_beam_search's table as it is),
+    n i32 [B, N] or [R] label counts, score f32 [B, N] or [R] the last stage's score (log domain); pivot i32 [B, P], 1 <= P <= N: the
+    slots whose tokens get a confidence (a decoder passes order[:, :n_best]).  Lp bounds the lengths (a slot with n > Lp - 1 is dead);
+    default T + 1, which no length exceeds - no host read is needed.
+    Returns (posterior f32 [R]: mbr_rescore's, bit for bit; conf f32 [B, P, Lp - 1]: for every token of the pivot the posterior mass
+    of the live slots whose alignment with the pivot matches it, 0 behind the pivot's length; hyp_conf f32 [B, P]: the posterior of
+    the pivot's slot[; match u8 [B, P, N, Lp - 1] with want_match: the votes themselves]).  A pivot outside 0 .. N-1 or naming a dead
+    slot gets zeros.  It is the share of the LIST's mass that agrees with a token - no calibrated probability.
+    The library sizes the workspace (about B * P * N * Lp^2 / 4 bytes); one above 2 GiB is refused with a ValueError."""
+    _dev(ids, n, score, pivot)
+    N = int(N)
+    R, B = _nbest_args("nbest_confidence", ids, n, score, N, "scores")
+    T = ids.shape[-1]
+    Lp = T + 1 if Lp is None else int(Lp)
+    if pivot.dtype != torch.int32 or pivot.dim() != 2 or pivot.shape[0] != B or not pivot.is_contiguous():
+        raise Js2tError(f"nbest_confidence: pivot = contiguous i32 [{B}, P] expected, got {pivot.dtype} {tuple(pivot.shape)}")
+    P = pivot.shape[1]
+    need = lib().js2t_nbest_confidence_workspace(B, P, N, Lp)
+    if need > CONFIDENCE_MAX_WORKSPACE:
+        raise ValueError(f"nbest_confidence: Lp {Lp}, P {P} and N {N} over {B} utterances need a workspace of {need} bytes, above "
+                         f"{CONFIDENCE_MAX_WORKSPACE}: pass fewer utterances or pivots per call, or a tighter Lp")
+    dev = ids.device
+    W = max(Lp - 1, 0)
+    posterior = torch.empty((R, ), dtype=torch.float32, device=dev)
+    conf = torch.empty((B, P, W), dtype=torch.float32, device=dev)
+    hyp_conf = torch.empty((B, P), dtype=torch.float32, device=dev)
+    match = torch.empty((B, P, N, W), dtype=torch.uint8, device=dev) if want_match else None
+    workspace = torch.empty((max(need, 0), ), dtype=torch.uint8, device=dev)  # (a refused shape: the entry point says why)
+    check(lib().js2t_nbest_confidence(_p(ids), T, _p(n), _p(score), _p(pivot), _p(posterior), _p(conf), _p(hyp_conf), _p(match),
+                                      _p(workspace), workspace.numel(), B, N, P, Lp, float(scale), _stream()), "js2t_nbest_confidence")
+    return (posterior, conf, hyp_conf, match) if want_match else (posterior, conf, hyp_conf)
+
+
 def attn_decode(q2d, k_view, v_view, ldkv: int, idx, idx_ld: int, Tmax: int, length: int, key_mask, H: int, dh: int, len_dev=None,
                 group: int = 1):
     """Single-query attention over cached keys / values (js2t_attn_decode).  k_view / v_view: tensors whose data_ptr is the

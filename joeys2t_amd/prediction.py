@@ -20,7 +20,7 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import _context_args, _decision_args, ctc_attention_rescore, ctc_beam_search, search
+from joeys2t_amd.search import _confidence_args, _context_args, _decision_args, ctc_attention_rescore, ctc_beam_search, search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
@@ -28,8 +28,8 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             return_prob: str = "none", repetition_penalty: float = -1, no_repeat_ngram_size: int = -1,
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
             decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
-            length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0, context=None,
-            context_weight: float = 0.0):
+            length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0,
+            confidence: bool = False, confidence_scale: float = 1.0, context=None, context_weight: float = 0.0):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -53,7 +53,13 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     context / context_weight (EXTENSION): contextual biasing - a joeys2t_amd.biasing.ContextGraph of phrases that matter for these
     batches and the boost per matched token, applied inside the CTC beam of either CTC decoder (`search.ctc_beam_search`); a phrase
     token outside a frame's `ctc_candidates` best labels is still not proposed.  The attention decoder refuses them; a weight that is
-    not finite, or non-zero without a graph, is refused before a model is touched."""
+    not finite, or non-zero without a graph, is refused before a model is touched.
+    confidence / confidence_scale (EXTENSION): token confidence from the n-best list of the two CTC decoders
+    (`search.ctc_beam_search`): the return value gains a LAST element {"token": [one np.float32 array per returned hypothesis, its
+    tokens' confidences, in the original order of the ids], "hypothesis": np.float32 array, each hypothesis' own posterior}.  It
+    says how much of the list's mass agrees with a token; it is no calibrated probability.  The attention decoder has no such list
+    and refuses them, return_prob="ref" runs no search and refuses them, and under a process group confidence=True is refused:
+    merging ragged per-token arrays across ranks is out of scope here."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
     if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
@@ -70,6 +76,14 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     if decoder == "attention" and mbr:
         raise ValueError("predict: decision='mbr' ranks the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
                          "no such list")
+    confidence, confidence_scale = _confidence_args("predict", confidence, confidence_scale)
+    if decoder == "attention" and confidence:
+        raise ValueError("predict: confidence=True votes over the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
+                         "no such list")
+    if confidence and return_prob == "ref":
+        raise ValueError("predict: confidence=True with return_prob='ref' (no search runs: there is no n-best list to vote)")
+    if confidence and use_ddp():
+        raise ValueError("predict: confidence=True under a process group (per-token arrays are not merged across ranks)")
     lm_kw = {} if lm is None and float(lm_weight) == 0.0 and float(length_bonus) == 0.0 else \
         dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
     if lm_fusion != "rescore":
@@ -78,6 +92,9 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         lm_kw = dict(lm_kw, decision="mbr", mbr_scale=mbr_scale)
     if biased:
         lm_kw = dict(lm_kw, context=context, context_weight=context_weight)
+    if confidence:
+        lm_kw = dict(lm_kw, confidence=True, confidence_scale=confidence_scale)
+    tok_conf, hyp_conf = [], []
     ctc = decoder in ("ctc", "ctc-attention")  # hypotheses of this rank's rows, whatever beam_size is
     model.eval()
     all_ids, all_scores, all_att, by_index = [], [], [], {}
@@ -106,11 +123,11 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             totals["n_correct"] += int(n_correct.sum().item())
             totals["ntokens"] += int(batch_ntokens.sum().item())
         if return_prob != "ref" and decoder == "ctc-attention":
-            ids, scores, _ = ctc_attention_rescore(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates,
-                                                   ctc_weight=ctc_weight, **lm_kw)
+            ids, scores, lens, *parts = ctc_attention_rescore(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates,
+                                                              ctc_weight=ctc_weight, **lm_kw)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref" and ctc:
-            ids, scores, _ = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates, **lm_kw)
+            ids, scores, lens, *parts = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates, **lm_kw)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref":
             ids, scores, att = search(model=model, batch=batch, beam_size=beam_size, beam_alpha=beam_alpha, n_best=n_best,
@@ -139,6 +156,9 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
                                         att[k] if att is not None else None)
         else:
             all_ids.extend(ids[sort_reverse_index])  # either hypotheses or references
+            if confidence:
+                tok_conf.extend(parts[0]["token_confidence"][i, :int(lens[i])].copy() for i in sort_reverse_index)
+                hyp_conf.extend(parts[0]["confidence"][sort_reverse_index])
             if att is not None:
                 all_att.extend(att[sort_reverse_index])
             if scores is not None and len(scores) == len(sort_reverse_index):
@@ -162,4 +182,6 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         valid_scores = {"loss": totals["loss"] / normalizer, "acc": totals["n_correct"] / totals["ntokens"],
                         "ppl": math.exp(totals["loss"] / totals["ntokens"])}  # upstream JoeyNMT; this reference leaves them NaN
         out.append({"totals": totals, "normalizer": normalizer, "valid_scores": valid_scores})
+    if confidence:
+        out.append({"token": tok_conf, "hypothesis": np.asarray(hyp_conf, dtype=np.float32)})
     return tuple(out)

@@ -537,6 +537,28 @@ def _decision_args(who, decision, mbr_scale):
     return decision == "mbr", mbr_scale
 
 
+def _confidence_args(who, confidence, confidence_scale):
+    """(token confidence wanted?, confidence_scale) of the confidence options of the two CTC decoders; refused before the model is
+    touched"""
+    confidence_scale = float(confidence_scale)
+    if not (math.isfinite(confidence_scale) and confidence_scale > 0.0):
+        raise ValueError(f"{who}: confidence_scale {confidence_scale} not finite and above 0")
+    if not confidence and confidence_scale != 1.0:
+        raise ValueError(f"{who}: confidence_scale {confidence_scale} without confidence=True (it scales the posterior of the votes)")
+    return bool(confidence), confidence_scale
+
+
+def _confidence_parts(parts, ids, n, score, N, order, n_best, scale, Lp, L):
+    """adds "token_confidence" f32 [B * n_best, L] (0 behind each row's length) and "confidence" f32 [B * n_best] to `parts`: the
+    votes of the whole list of N slots (js2t_nbest_confidence) for the tokens of the returned rows, order[:, :n_best]"""
+    B = order.shape[0]
+    _, conf, hyp = ops.nbest_confidence(ids, n, score.reshape(B * N), N, order[:, :n_best].contiguous(), scale, Lp=Lp)
+    conf = conf.reshape(B * n_best, Lp - 1).cpu().numpy()
+    tok = np.zeros((B * n_best, L), dtype=np.float32)
+    tok[:, :min(L, Lp - 1)] = conf[:, :L]
+    parts["token_confidence"], parts["confidence"] = tok, hyp.reshape(B * n_best).cpu().numpy()
+
+
 def _map_rank(order, B, N, dev):
     """i64 [B, N]: the rank of every slot by the model score - the inverse of the last stage's `order`; None: the list came best
     first, the rank of a slot is the slot"""
@@ -592,7 +614,8 @@ def _nbest_numpy(ids, n, score):
 
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
                     length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore", decision: str = "map",
-                    mbr_scale: float = 1.0, return_parts: bool = False, context=None, context_weight: float = 0.0):
+                    mbr_scale: float = 1.0, return_parts: bool = False, confidence: bool = False, confidence_scale: float = 1.0,
+                    context=None, context_weight: float = 0.0):
     """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
     `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
     `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
@@ -623,24 +646,36 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     bonus take part in that kernel only under lm_fusion="search"; under "rescore" they re-rank the biased list, the kernel's final
     score being the base of the n-gram stage.  Biasing adds no candidates: a phrase token that is not among a frame's `candidates`
     (<= 8) best labels is still not proposed.  return_parts gains "context" i32 [B * n_best], the matched tokens of every row.  A
-    weight that is not finite, or non-zero without a graph, is refused before the model is touched."""
+    weight that is not finite, or non-zero without a graph, is refused before the model is touched.
+    confidence=True (token confidence from the list, js2t_nbest_confidence): the list of `n_rescore` (default: beam_size) slots is
+    searched for and scored exactly as with decision="mbr" - n_rescore is accepted without an LM, and under lm_fusion="search" it is
+    the fused search's n_best - the ranking stays whatever `decision` says, and every token of the returned rows gets the posterior
+    mass, under softmax(confidence_scale * score), of the list entries whose Levenshtein alignment with the row matches it.  The
+    call then returns the parts dict as with return_parts=True, with two more entries: "token_confidence" f32 [B * n_best, L], 0
+    behind each row's length, and "confidence" f32 [B * n_best], the row's own posterior.  Ids, scores and lengths are those of the
+    same call without it; still no host read before the final copy.  It says how much of the LIST's mass agrees with a token: it is
+    no calibrated probability.  A scale that is not finite or not above 0, or one other than 1 without confidence=True, is refused
+    before the model is touched."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
     biased, context_weight = _context_args("ctc_beam_search", context, context_weight)
     fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
     mbr, mbr_scale = _decision_args("ctc_beam_search", decision, mbr_scale)
+    confidence, confidence_scale = _confidence_args("ctc_beam_search", confidence, confidence_scale)
+    wide = mbr or confidence  # the whole list of n_rescore slots is wanted, not the n_best first alone
+    return_parts = return_parts or confidence
     if not 1 <= n_best <= beam_size:
         raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
-    if fused and not mbr:
+    if fused and not wide:
         if n_rescore is not None:
             raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
-    elif rerank or mbr:
+    elif rerank or wide:
         n_rescore = int(beam_size if n_rescore is None else n_rescore)
         if not n_best <= n_rescore <= beam_size:
             raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
     elif n_rescore is not None:
         raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
     beam_size, n_best = int(beam_size), int(n_best)
-    N = n_rescore if mbr or (rerank and not fused) else n_best  # the slots searched for
+    N = n_rescore if wide or (rerank and not fused) else n_best  # the slots searched for
     with torch.no_grad():
         ids, n, ctc, score, (B, T, _), _, ctx = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
                                                                 length_bonus, context=context if biased else None,
@@ -652,6 +687,9 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
         map_rank = _map_rank(order, B, N, ids.device) if return_parts else None
         if mbr:  # the list ranked by its expected edit distance instead; Lp from the table's width: no length to read
             _, posterior, risk, order = ops.mbr_rescore(ids, n, score.reshape(B * N), N, mbr_scale, Lp=min(T, ops.edit_max_len()) + 1)
+        if confidence and order is None:  # the list as the search left it: the returned rows are its first slots
+            order = torch.arange(N, device=ids.device, dtype=torch.int32).expand(B, N)
+        full = (ids, n, score)
         if order is not None:
             rows, _ = _first_rows(order, n_best, N)
             ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score.reshape(B * N)[rows]
@@ -662,13 +700,16 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
             parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
         if biased:
             parts["context"] = (ctx.reshape(B * N)[rows] if order is not None else ctx.reshape(B * N)).cpu().numpy()
-    return (*_nbest_numpy(ids, n, score), parts)
+        out = _nbest_numpy(ids, n, score)
+        if confidence:  # Lp from the table's width, as the MBR stage's: no length to read
+            _confidence_parts(parts, *full, N, order, n_best, confidence_scale, min(T, ops.edit_max_len()) + 1, out[0].shape[1])
+    return (*out, parts)
 
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
                           n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
                           length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0,
-                          context=None, context_weight: float = 0.0):
+                          confidence: bool = False, confidence_scale: float = 1.0, context=None, context_weight: float = 0.0):
     """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
     of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
     over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
@@ -697,11 +738,17 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
     re-scored holds the labellings the phrases keep alive.  js2t_rescore takes the pure CTC score as ever; the context term,
     context_weight * the matched tokens of completed phrases, is added behind the n-gram stage and in front of the MBR decision
     (js2t_context_rescore), and its ranking decides.  The parts gain "context" i32 [B * n_best].  A weight that is not finite, or
-    non-zero without a graph, is refused before the model is touched."""
+    non-zero without a graph, is refused before the model is touched.
+    confidence / confidence_scale (token confidence from the list, `ctc_beam_search`): the votes are those of the n_rescore
+    hypotheses under softmax(confidence_scale * final score), for the tokens of the returned rows, whatever `decision` ranked them
+    by; the call returns the parts with "token_confidence" f32 [B * n_best, L] and "confidence" f32 [B * n_best] added.  Ids, scores
+    and lengths are those of the same call without it."""
     rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
     biased, context_weight = _context_args("ctc_attention_rescore", context, context_weight)
     fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
     mbr, mbr_scale = _decision_args("ctc_attention_rescore", decision, mbr_scale)
+    confidence, confidence_scale = _confidence_args("ctc_attention_rescore", confidence, confidence_scale)
+    return_parts = return_parts or confidence
     n_rescore = beam_size if n_rescore is None else n_rescore
     beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
     if not 1 <= n_best <= n_rescore <= beam_size <= 32:
@@ -748,4 +795,6 @@ def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, ca
             parts["map_rank"] = map_rank.reshape(B * N)[rows].cpu().numpy()
         if biased:
             parts["context"] = ctx[rows].cpu().numpy()
+        if confidence:
+            _confidence_parts(parts, ids, n, score, N, order, n_best, confidence_scale, min(Lp, ops.edit_max_len() + 1), out_ids.shape[1])
     return out_ids, out_score, out_n, parts
