@@ -103,15 +103,9 @@ extern "C" int64_t js2t_nbest_confidence_workspace(int64_t B, int32_t P, int32_t
 extern "C" int js2t_nbest_confidence(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* score, const int32_t* pivot,
                                      float* posterior, float* conf, float* hyp_conf, uint8_t* match, void* workspace,
                                      int64_t workspace_bytes, int64_t B, int32_t N, int32_t P, int64_t Lp, float scale, js2t_stream stream) {
-  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "nbest_confidence: N %d outside 1..%d", (int)N, NBEST_MAX_N);
+  if (const int rc = posterior_args("nbest_confidence", Lp, scale, "an alignment")) return rc;
+  if (const int rc = nbest_list_args("nbest_confidence", B, N, Lp, ids_stride, NBEST_PAIRS)) return rc;
   JS2T_CHECK(P >= 1 && P <= N, "nbest_confidence: P %d outside 1..N (%d)", (int)P, (int)N);
-  JS2T_CHECK(Lp >= 1, "nbest_confidence: Lp %lld below 1", (long long)Lp);
-  JS2T_CHECK(Lp - 1 <= JS2T_EDIT_MAX_LEN, "nbest_confidence: Lp - 1 = %lld above the longest row an alignment takes (%d)", (long long)(Lp - 1),
-             JS2T_EDIT_MAX_LEN);
-  JS2T_CHECK(scale > 0.f && scale <= 3.402823466e38f, "nbest_confidence: scale %g not finite and above 0", (double)scale);  // (a NaN fails too)
-  JS2T_CHECK(ids_stride >= Lp - 1, "nbest_confidence: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
-  JS2T_CHECK(B >= 0 && B < (int64_t(1) << 31) / (N * N), "nbest_confidence: bad shape (B %lld, N %d: B * N * N must stay below 2^31)", (long long)B,
-             (int)N);
   const int64_t need = js2t_nbest_confidence_workspace(B, P, N, Lp);
   JS2T_CHECK(workspace_bytes >= need, "nbest_confidence: workspace of %lld bytes below the %lld that B %lld, P %d, N %d, Lp %lld need",
              (long long)workspace_bytes, (long long)need, (long long)B, (int)P, (int)N, (long long)Lp);

@@ -51,16 +51,12 @@ extern "C" int js2t_context_rescore(const int64_t* ids, int64_t ids_stride, cons
                                     int64_t V, float context_weight, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(n && base_score && ctx && score && order, "context_rescore: null pointer");
-  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "context_rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
-  JS2T_CHECK(Lp >= 1, "context_rescore: Lp %lld below 1", (long long)Lp);
+  if (const int rc = nbest_list_args("context_rescore", B, N, Lp, ids_stride, NBEST_SLOTS)) return rc;  // (one wave per utterance: no B * N * Lp grid)
   context_view g;
   if (const int rc = context_args("context_rescore", ctx_nodes, ctx_edges, ctx_capacity, ctx_max_probe, ctx_n_nodes, ctx_max_fail, V,
                                   context_weight, &g))
     return rc;
   JS2T_CHECK(ids || context_weight == 0.f, "context_rescore: null pointer (ids, with context_weight %g)", (double)context_weight);
-  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31), "context_rescore: bad shape (B %lld, Lp %lld)",
-             (long long)B, (long long)Lp);
-  JS2T_CHECK(ids_stride >= Lp - 1, "context_rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
   hipLaunchKernelGGL(context_rescore_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, ids, ids_stride, n, base_score, g, ctx, score,
                      order, (int)N, Lp, context_weight);
   JS2T_LAUNCH_CHECK();

@@ -1,15 +1,12 @@
 // The ALIGNMENT behind the unit-cost Levenshtein distance of two rows of int64 ids, computed by ONE wave (EXTENSION; the reference
 // has no alignment on the device): which labels of the PIVOT row `a` are matched by the other row `b`.  confidence.hip calls it; the
 // table, the back-trace and its tie rule are stated in the header above js2t_nbest_confidence.  It is the sibling of editdist.hpp's
-// wave_edit_distance and shares its helpers; that function is untouched.
+// wave_edit_distance: the two share the walk of the table (edit_walk_tiles, where a tile's anti-diagonals are described) and the helpers.
 //
-// Forward pass.  The roles are not symmetric, so the orientation is fixed: the other row b lies across the lanes, 64 columns per
-// tile, every lane keeping its own symbol; the pivot runs down the rows.  A tile is walked by anti-diagonals exactly as in
-// editdist.hpp: at step t lane c owns cell (x, y) = (t - c, k0 + c + 1); `val` before the update is D[x-1][y], `left` the previous
-// lane's value of step t - 1, D[x][y-1], and `diag` what that shuffle returned the step before, D[x-1][y-1]; the pivot's symbols
-// ride from lane to lane; lane 63 leaves the tile's right boundary column in the wave's own LDS for lane 0 of the next tile.
-// Every cell additionally decides which of the header's four cases the back-trace takes there - that depends on its three
-// neighbours and the two symbols only - as a 2-bit code:
+// Forward pass.  The roles are not symmetric, so the orientation is fixed: the other row b lies across the lanes, the pivot runs down
+// the rows; at step t lane c owns cell (x, y) = (t - c, k0 + c + 1).  The walk runs with CODES: every cell additionally decides
+// which of the header's four cases the back-trace takes there - that depends on its three neighbours and the two symbols only - as
+// a 2-bit code:
 //     0 match (go to x-1, y-1, pivot position x-1 is matched)   1 substitution (x-1, y-1)   2 pivot label unmatched (x-1, y)
 //     3 (x, y-1)
 // A lane packs the codes of 16 consecutive rows of its column into one word and stores it at
@@ -17,7 +14,7 @@
 // (a vector store; m = the pivot's trimmed length), so the pair's region holds align_code_words(longest row) words.  A table of
 // one tile (k <= 64) and at most ALIGN_LDS_BLKS blocks of 16 rows (m <= 256) - every pair of the lists a beam search returns for
 // an utterance of a few seconds - keeps its codes in the wave's LDS instead, under the same index: the boundary column, which only a
-// second tile would read, is not written then, and its 4 KB hold the 16 x 64 words.
+// second tile would read, is not written then (the walk runs without BND_ALWAYS), and its 4 KB hold the 16 x 64 words.
 //
 // Back-trace.  Behind a fence (codes in global memory only) all lanes walk the codes back from (m, k) in lockstep (every bound is wave-uniform; one word is
 // loaded per step, the same for every lane) until a border of the table is reached: along x = 0 and y = 0 nothing is matched.  Lane w
@@ -60,43 +57,7 @@ __device__ __forceinline__ uint32_t wave_edit_align(const int64_t* a, int m, con
   const int xblks = (m + 15) >> 4;
   const bool in_lds = k <= 64 && xblks <= ALIGN_LDS_BLKS;  // (wave-uniform) the codes stay in the wave's LDS
   uint32_t* lcodes = reinterpret_cast<uint32_t*>(bnd);
-  for (int k0 = 0; k0 < k; k0 += 64) {  // (every bound below is wave-uniform: all lanes reach every shuffle)
-    const int cols = k - k0 < 64 ? k - k0 : 64;
-    const bool col = lane < cols, more = k0 + 64 < k;  // more: a next tile reads this one's boundary column
-    const int64_t bs = col ? b[k0 + lane] : 0;
-    uint32_t* tile = codes + (int64_t)(k0 >> 6) * xblks * 64;
-    int val = k0 + lane + 1;  // row 0 of the table
-    int diag = k0;            // (lane 0's: row 0 of the boundary column; every other lane's comes with the first shuffle)
-    int64_t as = 0, chunk = 0;
-    uint32_t cw = 0;
-    const int steps = m + cols - 1;
-    for (int t = 1; t <= steps; ++t) {
-      if (((t - 1) & 63) == 0) chunk = t - 1 + lane < m ? a[t - 1 + lane] : 0;
-      int left = __shfl_up(val, 1, 64);
-      as = edit_shfl_up1(as);
-      const int64_t head = edit_read_lane(chunk, (t - 1) & 63);
-      if (lane == 0) {
-        as = head;
-        left = k0 ? (int)bnd[t < m ? t : m] : t;
-      }
-      const int x = t - lane;  // the row this lane is in
-      if (col && x >= 1 && x <= m) {
-        const bool eq = as == bs;
-        const int sub = diag + (eq ? 0 : 1), del = val + 1, ins = left + 1;
-        const int d = sub < del ? (sub < ins ? sub : ins) : (del < ins ? del : ins);
-        const uint32_t code = (eq && d == diag) ? 0u : d == diag + 1 ? 1u : d == del ? 2u : 3u;  // the FIRST case that applies
-        val = d;
-        if (lane == 63 && more) bnd[x] = (uint16_t)val;
-        cw |= code << (((x - 1) & 15) * 2);
-        if (((x - 1) & 15) == 15 || x == m) {
-          if (in_lds) lcodes[((x - 1) >> 4) * 64 + lane] = cw;
-          else tile[(int64_t)((x - 1) >> 4) * 64 + lane] = cw;
-          cw = 0;
-        }
-      }
-      diag = left;
-    }
-  }
+  edit_walk_tiles<true, false>(a, m, b, k, bnd, codes, in_lds, lane);  // the pivot down the rows, b across the lanes
 #ifdef JS2T_ALIGN_SKIP_TRACE  // timing builds of tools/confidence_bench.py only: the forward pass and its codes, no back-trace (wrong votes)
   return mask;
 #endif

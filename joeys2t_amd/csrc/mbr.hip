@@ -104,13 +104,8 @@ extern "C" int js2t_edit_distance(const int64_t* a, int64_t a_stride, const int3
 extern "C" int js2t_mbr_rescore(const int64_t* ids, int64_t ids_stride, const int32_t* n, const float* score, int32_t* dist,
                                 float* posterior, float* risk, int32_t* order, int64_t B, int32_t N, int64_t Lp, float scale,
                                 js2t_stream stream) {
-  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "mbr_rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
-  JS2T_CHECK(Lp >= 1, "mbr_rescore: Lp %lld below 1", (long long)Lp);
-  JS2T_CHECK(Lp - 1 <= JS2T_EDIT_MAX_LEN, "mbr_rescore: Lp - 1 = %lld above the longest row an edit distance takes (%d)", (long long)(Lp - 1),
-             JS2T_EDIT_MAX_LEN);
-  JS2T_CHECK(scale > 0.f && scale <= 3.402823466e38f, "mbr_rescore: scale %g not finite and above 0", (double)scale);  // (a NaN fails too)
-  JS2T_CHECK(ids_stride >= Lp - 1, "mbr_rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
-  JS2T_CHECK(B >= 0 && B < (int64_t(1) << 31) / (N * N), "mbr_rescore: bad shape (B %lld, N %d: B * N * N must stay below 2^31)", (long long)B, (int)N);
+  if (const int rc = posterior_args("mbr_rescore", Lp, scale, "an edit distance")) return rc;
+  if (const int rc = nbest_list_args("mbr_rescore", B, N, Lp, ids_stride, NBEST_PAIRS)) return rc;
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(n && score && dist && posterior && risk && order && (ids || Lp == 1), "mbr_rescore: null pointer");
   const int64_t pairs = B * (N * (N - 1) / 2);

@@ -1,12 +1,31 @@
 // The rules the n-best entry points share (EXTENSION; the reference has no n-best list): js2t_ctc_beam_search(_lm, _ctx) writes the list,
-// js2t_rescore, js2t_ngram_rescore, js2t_context_rescore and js2t_mbr_rescore re-rank it, and they compose because each of these rules exists once, here.
-// The semantics are stated in the header; rescore.hip, ngram.hip, context.hip, ctc_beam.hip and mbr.hip are the files that apply them.
+// js2t_rescore, js2t_ngram_rescore, js2t_context_rescore and js2t_mbr_rescore re-rank it, js2t_nbest_confidence votes over it, and they compose because each of
+// these rules exists once, here: the limit on N, the shape a list may have (nbest_list_args, host), the dead slot, the ranking, the fused score, the hash.
+// The semantics are stated in the header; rescore.hip, ngram.hip, context.hip, ctc_beam.hip, mbr.hip and confidence.hip are the files that apply them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
+#include "common.hpp"
+
 constexpr int NBEST_MAX_N = 32;  // slots of one utterance: one lane each, half a wave
+
+// The shape of a list an entry point takes, refused through JS2T_CHECK's path: N in 1 .. NBEST_MAX_N, Lp >= 1 positions (labels and EOS) per row,
+// rows of ids at least Lp - 1 apart, and B small enough for what the entry point's grids and 32-bit offsets count beside the B * NBEST_MAX_N slots -
+// NBEST_ROWS: the B * N * Lp positions; NBEST_PAIRS (quadratic in N; B may be 0): the B * N * N pairs; NBEST_SLOTS: nothing more.
+enum nbest_extent { NBEST_SLOTS, NBEST_ROWS, NBEST_PAIRS };
+inline int nbest_list_args(const char* who, int64_t B, int32_t N, int64_t Lp, int64_t ids_stride, nbest_extent extent) {
+  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "%s: N %d outside 1..%d", who, (int)N, NBEST_MAX_N);
+  JS2T_CHECK(Lp >= 1, "%s: Lp %lld below 1", who, (long long)Lp);
+  JS2T_CHECK(ids_stride >= Lp - 1, "%s: ids_stride %lld below Lp - 1 (%lld)", who, (long long)ids_stride, (long long)(Lp - 1));
+  if (extent == NBEST_PAIRS)
+    JS2T_CHECK(B >= 0 && B < (int64_t(1) << 31) / (N * N), "%s: bad shape (B %lld, N %d: B * N * N must stay below 2^31)", who, (long long)B, (int)N);
+  else
+    JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31) && (extent == NBEST_SLOTS || B * N * Lp < (int64_t(1) << 31)),
+               "%s: bad shape (B %lld, Lp %lld)", who, (long long)B, (long long)Lp);
+  return JS2T_OK;
+}
 
 // a slot that holds no hypothesis: no score, or a length that does not fit the Lp positions (labels and EOS) of its row
 __device__ __forceinline__ bool nbest_dead(float score, int n, int64_t Lp) { return score == -INFINITY || n < 0 || (int64_t)n > Lp - 1; }

@@ -75,13 +75,9 @@ extern "C" int js2t_ngram_rescore(const int64_t* ids, int64_t ids_stride, const 
                                   int64_t eos, float lm_weight, float length_bonus, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(ids && n && base_score && lm_score && score && order, "ngram_rescore: null pointer");
-  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "ngram_rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
-  JS2T_CHECK(Lp >= 1, "ngram_rescore: Lp %lld below 1", (long long)Lp);
+  if (const int rc = nbest_list_args("ngram_rescore", B, N, Lp, ids_stride, NBEST_ROWS)) return rc;
   ngram_view lm;
   if (const int rc = ngram_args("ngram_rescore", uni, table, capacity, max_probe, lm_order, V, bos, eos, lm_weight, length_bonus, &lm)) return rc;
-  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
-             "ngram_rescore: bad shape (B %lld, Lp %lld)", (long long)B, (long long)Lp);
-  JS2T_CHECK(ids_stride >= Lp - 1, "ngram_rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
   const int64_t R = B * N;
   hipLaunchKernelGGL(ngram_score_kernel, dim3((unsigned)cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, ids, ids_stride, n, base_score, lm,
                      lm_tok, lm_score, score, R, Lp, bos, eos, lm_weight, length_bonus);

@@ -4,6 +4,15 @@
 #pragma once
 #include "common.hpp"
 #include "nbest.hpp"
+#include "editdist.hpp"
+
+// what the two entry points ask beyond the list's shape, in front of it (a row too long for the table would also fail the stride rule, and this says
+// why): rows an edit table takes - `what` names the table in the error - and a scale that is finite and above 0
+inline int posterior_args(const char* who, int64_t Lp, float scale, const char* what) {
+  JS2T_CHECK(Lp - 1 <= JS2T_EDIT_MAX_LEN, "%s: Lp - 1 = %lld above the longest row %s takes (%d)", who, (long long)(Lp - 1), what, JS2T_EDIT_MAX_LEN);
+  JS2T_CHECK(scale > 0.f && scale <= 3.402823466e38f, "%s: scale %g not finite and above 0", who, (double)scale);  // (a NaN fails too)
+  return JS2T_OK;
+}
 
 // a slot without posterior mass: dead by the rule of the list, or a score that is no log mass (NaN, +inf)
 __device__ __forceinline__ bool mbr_dead(float score, int n, int64_t Lp) { return nbest_dead(score, n, Lp) || score != score || score == INFINITY; }

@@ -157,14 +157,10 @@ extern "C" int js2t_rescore(const void* logits, int dt, const int64_t* ids, int6
                             int64_t eos, float ctc_weight, js2t_stream stream) {
   if (B == 0) return JS2T_OK;
   JS2T_CHECK(logits && ids && n && ctc_score && tok_lp && att_score && score && order, "rescore: null pointer");
-  JS2T_CHECK(N >= 1 && N <= NBEST_MAX_N, "rescore: N %d outside 1..%d", (int)N, NBEST_MAX_N);
-  JS2T_CHECK(Lp >= 1, "rescore: Lp %lld below 1", (long long)Lp);
+  if (const int rc = nbest_list_args("rescore", B, N, Lp, ids_stride, NBEST_ROWS)) return rc;
   JS2T_CHECK(V >= 2 && V < 0x7fffffff, "rescore: V %lld outside 2..2^31-2", (long long)V);
-  JS2T_CHECK(B > 0 && B < (int64_t(1) << 31) / NBEST_MAX_N && Lp < (int64_t(1) << 31) && B * N * Lp < (int64_t(1) << 31),
-             "rescore: bad shape (B %lld, Lp %lld)", (long long)B, (long long)Lp);
   JS2T_CHECK(eos >= 0 && eos < V, "rescore: eos %lld outside the vocabulary", (long long)eos);
   JS2T_CHECK(ctc_weight >= 0.f && ctc_weight <= 1.f, "rescore: ctc_weight %g outside [0, 1]", (double)ctc_weight);  // (NaN fails too)
-  JS2T_CHECK(ids_stride >= Lp - 1, "rescore: ids_stride %lld below Lp - 1 (%lld)", (long long)ids_stride, (long long)(Lp - 1));
   JS2T_CHECK(dt == JS2T_F32 || dt == JS2T_BF16, "bad dtype %d", dt);
   const int64_t rows = B * N * Lp;
   if (dt == JS2T_F32)

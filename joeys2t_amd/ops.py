@@ -934,26 +934,20 @@ def context_rescore(ids, n, base_score, N: int, context, context_weight: float, 
     out: (ctx, score, order) to write instead of fresh ones, contiguous."""
     _dev(ids, n, base_score, *(out or ()))
     N = int(N)
-    R, B = _nbest_args("context_rescore", ids, n, base_score, N, "scores")
-    T = ids.shape[-1]
-    Lp = T + 1 if Lp is None else int(Lp)
+    R, B, T, Lp = _nbest_args("context_rescore", ids, n, base_score, N, "scores", Lp=Lp)
     nodes, edges, ccap, cprobe, n_nodes, max_fail = _context_args("context_rescore", context, context_weight, ids.device, "hypotheses", None)
-    want = (((R, ), torch.int32), ((R, ), torch.float32), ((B, N), torch.int32))
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=ids.device) for s, d in want)
-    elif len(out) != 3 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
-        raise Js2tError(f"context_rescore: out = contiguous (i32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
-    ctx, score, order = out
+    ctx, score, order = _nbest_out("context_rescore", out, (((R, ), torch.int32), ((R, ), torch.float32), ((B, N), torch.int32)), ids.device)
     check(lib().js2t_context_rescore(_p(ids), T, _p(n), _p(base_score), _p(nodes), _p(edges), ccap, cprobe, n_nodes, max_fail, _p(ctx),
                                      _p(score), _p(order), B, N, Lp, context.V if context is not None else 1, float(context_weight),
                                      _stream()), "js2t_context_rescore")
     return ctx, score, order
 
 
-def _nbest_args(who, ids, n, score, N, scores, R=None):
-    """The checks of an n-best list - ids i64 [B, N, T] or [R, T], n i32 and score f32 of R = B * N hypotheses - for the two entry
-    points that re-rank one.  R: the count the caller's logits fix; None: the list itself says it.  Returns (R, B); `who` names the
-    caller in the errors and `scores` its score."""
+def _nbest_args(who, ids, n, score, N, scores, R=None, Lp=None):
+    """The checks of an n-best list - ids i64 [B, N, T] or [R, T], n i32 and score f32 of R = B * N hypotheses - for the entry
+    points that take one.  R: the count the caller's logits fix; None: the list itself says it.  Lp: the caller's bound on the
+    lengths; None: T + 1, which no length exceeds.  Returns (R, B, T, Lp); `who` names the caller in the errors and `scores` its
+    score."""
     if N < 1:  # (no [B, N] to allocate for the library to refuse)
         raise Js2tError(f"{who}: N {N} outside 1..32")
     ids_ok = ids.dim() in (2, 3) and ids.dtype == torch.int64 and ids.is_contiguous()
@@ -967,21 +961,29 @@ def _nbest_args(who, ids, n, score, N, scores, R=None):
             or not score.is_contiguous():
         raise Js2tError(f"{who}: contiguous i32 lengths and f32 {scores} of {R} hypotheses expected, got {n.dtype} {tuple(n.shape)} and "
                         f"{score.dtype} {tuple(score.shape)}")
-    return R, R // N
+    T = ids.shape[-1]
+    return R, R // N, T, T + 1 if Lp is None else int(Lp)
 
 
-def _nbest_out(who, out, R, Lp, B, N, dev, tok=True, tok_optional=False):
-    """The four outputs of a re-ranking - per-token values f32 [R, Lp], two scores f32 [R], order i32 [B, N] - fresh ones (the
-    first None without `tok`), or the caller's `out`, checked; tok_optional: its first may be None."""
-    want = (((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
+_DT_NAME = {torch.float32: "f32", torch.int32: "i32", torch.uint8: "u8"}
+
+
+def _nbest_out(who, out, want, dev, optional=(), absent=()):
+    """The outputs of an entry point over an n-best list.  want: their ((shape, dtype), ...).  out None: fresh ones, None at the
+    positions in `absent`; else the caller's `out`, checked - as many, contiguous, those shapes and dtypes - where the positions in
+    `optional` may hold None."""
     if out is None:
-        return (torch.empty((R, max(Lp, 0)), dtype=torch.float32, device=dev) if tok else None,
-                *(torch.empty(s, dtype=d, device=dev) for s, d in want[1:]))
-    given = [(t, w) for t, w in zip(out, want) if not (tok_optional and t is None and w is want[0])]
-    if len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in given):
-        raise Js2tError(f"{who}: out = contiguous (f32 [{R}, {Lp}]{' or None' if tok_optional else ''}, f32 [{R}], f32 [{R}], i32 [{B}, {N}]) "
-                        "expected")
+        return tuple(None if k in absent else torch.empty(tuple(max(d, 0) for d in s), dtype=dt, device=dev) for k, (s, dt) in enumerate(want))
+    given = [(t, w) for k, (t, w) in enumerate(zip(out, want)) if not (k in optional and t is None)]
+    if len(out) != len(want) or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in given):
+        names = ", ".join(f"{_DT_NAME[d]} [{', '.join(map(str, s))}]{' or None' if k in optional else ''}" for k, (s, d) in enumerate(want))
+        raise Js2tError(f"{who}: out = contiguous {names if len(want) == 1 else '(' + names + ')'} expected")
     return out
+
+
+def _rerank_outputs(R, Lp, B, N):
+    """the four outputs of a re-ranking: per-token values f32 [R, Lp], two scores f32 [R], order i32 [B, N]"""
+    return ((R, Lp), torch.float32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32)
 
 
 def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, out=None):
@@ -999,8 +1001,8 @@ def rescore(logits3d, ids, n, ctc_score, N: int, eos: int, ctc_weight: float, ou
     N = int(N)
     if R and (logits3d.stride(2) != 1 or logits3d.stride(1) != V or logits3d.stride(0) != Lp * V):
         raise Js2tError(f"rescore: logits with dense rows expected, got strides {logits3d.stride()} for {tuple(logits3d.shape)}")
-    R, B = _nbest_args("rescore", ids, n, ctc_score, N, "CTC scores", R)
-    tok_lp, att, score, order = _nbest_out("rescore", out, R, Lp, B, N, logits3d.device)
+    R, B, _, _ = _nbest_args("rescore", ids, n, ctc_score, N, "CTC scores", R)
+    tok_lp, att, score, order = _nbest_out("rescore", out, _rerank_outputs(R, Lp, B, N), logits3d.device)
     check(lib().js2t_rescore(_p(logits3d), dt_code(logits3d), _p(ids), ids.shape[-1], _p(n), _p(ctc_score), _p(tok_lp), _p(att), _p(score),
                              _p(order), B, N, Lp, V, int(eos), float(ctc_weight), _stream()), "js2t_rescore")
     return tok_lp, att, score, order
@@ -1019,11 +1021,10 @@ def ngram_rescore(ids, n, base_score, N: int, lm, bos: int, eos: int, lm_weight:
     out: the output tensors to write instead of fresh ones: (lm_tok or None, lm_score, score, order), contiguous."""
     _dev(ids, n, base_score, *(t for t in (out or ()) if t is not None))
     N = int(N)
-    R, B = _nbest_args("ngram_rescore", ids, n, base_score, N, "scores")
-    T = ids.shape[-1]
-    Lp = T + 1 if Lp is None else int(Lp)
+    R, B, T, Lp = _nbest_args("ngram_rescore", ids, n, base_score, N, "scores", Lp=Lp)
     uni, table, capacity, max_probe, order_lm, V = _lm_args("ngram_rescore", lm, lm_weight, ids.device, "hypotheses", V, own_V=True)
-    lm_tok, lm_score, score, order = _nbest_out("ngram_rescore", out, R, Lp, B, N, ids.device, tok=want_tokens, tok_optional=True)
+    lm_tok, lm_score, score, order = _nbest_out("ngram_rescore", out, _rerank_outputs(R, Lp, B, N), ids.device, optional=(0, ),
+                                                absent=() if want_tokens else (0, ))
     check(lib().js2t_ngram_rescore(_p(ids), T, _p(n), _p(base_score), _p(uni), _p(table), capacity, max_probe, order_lm, _p(lm_tok),
                                    _p(lm_score), _p(score), _p(order), B, N, Lp, int(V), int(bos), int(eos), float(lm_weight),
                                    float(length_bonus), _stream()), "js2t_ngram_rescore")
@@ -1060,10 +1061,7 @@ def edit_distance(a, a_len, b, b_len, group: int = 1, out=None):
     Rb, b_stride = _id_rows("edit_distance", "b", b, b_len)
     if Rb != -(-R // group):
         raise Js2tError(f"edit_distance: {R} rows in groups of {group} need {-(-R // group)} rows of b, got {Rb}")
-    if out is None:
-        out = torch.empty((R, ), dtype=torch.int32, device=a.device)
-    elif tuple(out.shape) != (R, ) or out.dtype != torch.int32 or not out.is_contiguous():
-        raise Js2tError(f"edit_distance: out = contiguous i32 [{R}] expected")
+    out, = _nbest_out("edit_distance", None if out is None else (out, ), (((R, ), torch.int32), ), a.device)
     check(lib().js2t_edit_distance(_p(a), a_stride, _p(a_len), _p(b), b_stride, _p(b_len), _p(out), R, group, a.shape[1], b.shape[1],
                                    _stream()), "js2t_edit_distance")
     return out
@@ -1080,15 +1078,9 @@ def mbr_rescore(ids, n, score, N: int, scale: float = 1.0, Lp: int = None, out=N
     out: the four output tensors to write instead of fresh ones (contiguous, those shapes and dtypes)."""
     _dev(ids, n, score, *(out or ()))
     N = int(N)
-    R, B = _nbest_args("mbr_rescore", ids, n, score, N, "scores")
-    T = ids.shape[-1]
-    Lp = T + 1 if Lp is None else int(Lp)
-    want = (((B, N, N), torch.int32), ((R, ), torch.float32), ((R, ), torch.float32), ((B, N), torch.int32))
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=ids.device) for s, d in want)
-    elif len(out) != 4 or any(t is None or tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
-        raise Js2tError(f"mbr_rescore: out = contiguous (i32 [{B}, {N}, {N}], f32 [{R}], f32 [{R}], i32 [{B}, {N}]) expected")
-    dist, posterior, risk, order = out
+    R, B, T, Lp = _nbest_args("mbr_rescore", ids, n, score, N, "scores", Lp=Lp)
+    dist, posterior, risk, order = _nbest_out("mbr_rescore", out, (((B, N, N), torch.int32), ((R, ), torch.float32), ((R, ), torch.float32),
+                                                                   ((B, N), torch.int32)), ids.device)
     check(lib().js2t_mbr_rescore(_p(ids), T, _p(n), _p(score), _p(dist), _p(posterior), _p(risk), _p(order), B, N, Lp, float(scale),
                                  _stream()), "js2t_mbr_rescore")
     return dist, posterior, risk, order
@@ -1109,9 +1101,7 @@ def nbest_confidence(ids, n, score, N: int, pivot, scale: float = 1.0, Lp: int =
     The library sizes the workspace (about B * P * N * Lp^2 / 4 bytes); one above 2 GiB is refused with a ValueError."""
     _dev(ids, n, score, pivot)
     N = int(N)
-    R, B = _nbest_args("nbest_confidence", ids, n, score, N, "scores")
-    T = ids.shape[-1]
-    Lp = T + 1 if Lp is None else int(Lp)
+    R, B, T, Lp = _nbest_args("nbest_confidence", ids, n, score, N, "scores", Lp=Lp)
     if pivot.dtype != torch.int32 or pivot.dim() != 2 or pivot.shape[0] != B or not pivot.is_contiguous():
         raise Js2tError(f"nbest_confidence: pivot = contiguous i32 [{B}, P] expected, got {pivot.dtype} {tuple(pivot.shape)}")
     P = pivot.shape[1]
@@ -1119,13 +1109,9 @@ def nbest_confidence(ids, n, score, N: int, pivot, scale: float = 1.0, Lp: int =
     if need > CONFIDENCE_MAX_WORKSPACE:
         raise ValueError(f"nbest_confidence: Lp {Lp}, P {P} and N {N} over {B} utterances need a workspace of {need} bytes, above "
                          f"{CONFIDENCE_MAX_WORKSPACE}: pass fewer utterances or pivots per call, or a tighter Lp")
-    dev = ids.device
-    W = max(Lp - 1, 0)
-    posterior = torch.empty((R, ), dtype=torch.float32, device=dev)
-    conf = torch.empty((B, P, W), dtype=torch.float32, device=dev)
-    hyp_conf = torch.empty((B, P), dtype=torch.float32, device=dev)
-    match = torch.empty((B, P, N, W), dtype=torch.uint8, device=dev) if want_match else None
-    workspace = torch.empty((max(need, 0), ), dtype=torch.uint8, device=dev)  # (a refused shape: the entry point says why)
+    posterior, conf, hyp_conf, match, workspace = _nbest_out(  # (a refused shape, Lp < 1 or need < 0: the entry point says why)
+        "nbest_confidence", None, (((R, ), torch.float32), ((B, P, Lp - 1), torch.float32), ((B, P), torch.float32),
+                                   ((B, P, N, Lp - 1), torch.uint8), ((need, ), torch.uint8)), ids.device, absent=() if want_match else (3, ))
     check(lib().js2t_nbest_confidence(_p(ids), T, _p(n), _p(score), _p(pivot), _p(posterior), _p(conf), _p(hyp_conf), _p(match),
                                       _p(workspace), workspace.numel(), B, N, P, Lp, float(scale), _stream()), "js2t_nbest_confidence")
     return (posterior, conf, hyp_conf, match) if want_match else (posterior, conf, hyp_conf)

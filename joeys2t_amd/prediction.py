@@ -20,7 +20,9 @@ import torch
 from joeys2t_amd.batch import Batch
 from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
-from joeys2t_amd.search import _confidence_args, _context_args, _decision_args, ctc_attention_rescore, ctc_beam_search, search
+from joeys2t_amd.ctc_search import (confidence_args, context_args, ctc_attention_rescore, ctc_beam_search, decision_args, lm_fusion_arg,
+                                     lm_given)
+from joeys2t_amd.search import search
 
 
 def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: float = -1.0, n_best: int = 1,
@@ -62,21 +64,20 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     merging ragged per-token arrays across ranks is out of scope here."""
     if decoder not in ("attention", "ctc", "ctc-attention"):
         raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
-    if decoder == "attention" and (lm is not None or float(lm_weight) != 0.0 or float(length_bonus) != 0.0):
+    if decoder == "attention" and lm_given(lm, lm_weight, length_bonus):
         raise ValueError("predict: lm / lm_weight / length_bonus re-rank the n-best list of decoder='ctc' or 'ctc-attention'; "
                          "decoder='attention' cannot apply them")
-    if lm_fusion not in ("rescore", "search"):
-        raise ValueError(f"predict: lm_fusion '{lm_fusion}' is neither 'rescore' nor 'search'")
+    lm_fusion_arg("predict", lm_fusion)  # (the value alone: without an lm or a bonus the decoder refuses "search")
     if decoder == "attention" and lm_fusion != "rescore":
         raise ValueError("predict: lm_fusion applies to the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
-    mbr, mbr_scale = _decision_args("predict", decision, mbr_scale)
-    biased, context_weight = _context_args("predict", context, context_weight)
+    mbr, mbr_scale = decision_args("predict", decision, mbr_scale)
+    biased, context_weight = context_args("predict", context, context_weight)
     if decoder == "attention" and (context is not None or biased):
         raise ValueError("predict: context / context_weight bias the CTC beam of decoder='ctc' or 'ctc-attention'; decoder='attention' has none")
     if decoder == "attention" and mbr:
         raise ValueError("predict: decision='mbr' ranks the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
                          "no such list")
-    confidence, confidence_scale = _confidence_args("predict", confidence, confidence_scale)
+    confidence, confidence_scale = confidence_args("predict", confidence, confidence_scale)
     if decoder == "attention" and confidence:
         raise ValueError("predict: confidence=True votes over the n-best list of decoder='ctc' or 'ctc-attention'; decoder='attention' has "
                          "no such list")
@@ -84,7 +85,7 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         raise ValueError("predict: confidence=True with return_prob='ref' (no search runs: there is no n-best list to vote)")
     if confidence and use_ddp():
         raise ValueError("predict: confidence=True under a process group (per-token arrays are not merged across ranks)")
-    lm_kw = {} if lm is None and float(lm_weight) == 0.0 and float(length_bonus) == 0.0 else \
+    lm_kw = {} if not lm_given(lm, lm_weight, length_bonus) else \
         dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
     if lm_fusion != "rescore":
         lm_kw = dict(lm_kw, lm_fusion=lm_fusion)  # (without an lm or a bonus the decoder refuses it)

@@ -17,7 +17,6 @@ between those stages, so with any of them on the step runs as js2t_log_softmax -
     to 0 AFTER the forbidden ids were masked; the prompt mask is embedded and added to the decoder input (model.py:271-282),
     which needs the full-prefix decoder pass (no KV cache on this path);
   * `return_attention` (greedy only, :318-325): cross-attention weights of the last layer, full-prefix pass."""
-import math
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -469,332 +468,5 @@ def search(model, batch, max_output_length: int, beam_size: int, beam_alpha: flo
     return _np(out), _np(scores), _np(att)
 
 
-def ctc_greedy(model, batch):
-    """CTC best-path decoding of the encoder-side output layer (the reference's `decode_ctc` return type hands
-    out ctc_out, model.py:162-166, without a consumer): encode once, project with `decoder.ctc_output_layer`, take the
-    frame-wise arg-max inside each utterance's sub-sampled length (model.py:125), merge repeats, drop blanks
-    (blank = BOS, model.py:84).  Returns NumPy (ids i64[B, T'] pad-filled, lengths i64[B])."""
-    from joeys2t_amd import ops
-    layer = getattr(model.decoder, "ctc_output_layer", None)
-    if layer is None:
-        raise ValueError("ctc_greedy: the model has no CTC output layer (loss: crossentropy-ctc)")
-    with torch.no_grad():
-        encoder_output, _, src_mask, _ = model(return_type="encode", **vars(batch))
-        ctc_out = model.decoder.project(layer, encoder_output, model.runtime.compute_dtype)  # [B, T', V]
-        B, T, V = ctc_out.shape
-        _, best = ops.row_lse(ctc_out.reshape(B * T, V), want_argmax=True)
-        in_len = src_mask.squeeze(1).sum(dim=1)
-        ids, n = ops.ctc_collapse(best.view(B, T), in_len, model.bos_index, model.pad_index)
-    return ids.cpu().numpy(), n.cpu().numpy()
-
-
-
-def _ngram_args(who, lm, lm_weight, length_bonus):
-    """(re-rank at all?, lm_weight, length_bonus) of the LM options of the two CTC decoders; refused before the model is touched"""
-    lm_weight, length_bonus = float(lm_weight), float(length_bonus)
-    if not (math.isfinite(lm_weight) and math.isfinite(length_bonus)):
-        raise ValueError(f"{who}: lm_weight {lm_weight} / length_bonus {length_bonus} not finite")
-    if lm is None and lm_weight != 0.0:
-        raise ValueError(f"{who}: lm_weight {lm_weight} without an lm")
-    return lm is not None or length_bonus != 0.0, lm_weight, length_bonus
-
-
-def _ngram_rerank(model, ids, n, base, N, lm, lm_weight, length_bonus, dev, **kw):
-    """ops.ngram_rescore of the beam kernel's [B, N, T] table over the model's vocabulary, the lm moved to the device if need be"""
-    if lm is not None and lm.device != dev:
-        lm.to(dev)
-    return ops.ngram_rescore(ids, n, base, N, lm, model.bos_index, model.eos_index, lm_weight, length_bonus, V=len(model.trg_vocab), **kw)
-
-
-def _lm_fusion_arg(who, lm_fusion, rerank):
-    """is the LM fused into the beam ("search") instead of re-ranking its n-best list ("rescore", the default)?"""
-    if lm_fusion not in ("rescore", "search"):
-        raise ValueError(f"{who}: lm_fusion '{lm_fusion}' is neither 'rescore' nor 'search'")
-    if lm_fusion == "search" and not rerank:
-        raise ValueError(f"{who}: lm_fusion='search' without an lm or a length_bonus")
-    return lm_fusion == "search"
-
-
-def _context_args(who, context, context_weight):
-    """(bias at all?, context_weight) of the contextual-biasing options of the two CTC decoders; refused before the model is touched"""
-    context_weight = float(context_weight)
-    if not math.isfinite(context_weight):
-        raise ValueError(f"{who}: context_weight {context_weight} not finite")
-    if context is None and context_weight != 0.0:
-        raise ValueError(f"{who}: context_weight {context_weight} without a context graph")
-    return context is not None and context_weight != 0.0, context_weight
-
-
-def _decision_args(who, decision, mbr_scale):
-    """(rank by minimum Bayes risk?, mbr_scale) of the decision options of the two CTC decoders; refused before the model is touched"""
-    if decision not in ("map", "mbr"):
-        raise ValueError(f"{who}: decision '{decision}' is neither 'map' nor 'mbr'")
-    mbr_scale = float(mbr_scale)
-    if not (math.isfinite(mbr_scale) and mbr_scale > 0.0):
-        raise ValueError(f"{who}: mbr_scale {mbr_scale} not finite and above 0")
-    if decision == "map" and mbr_scale != 1.0:
-        raise ValueError(f"{who}: mbr_scale {mbr_scale} with decision='map' (it scales the posterior of decision='mbr')")
-    return decision == "mbr", mbr_scale
-
-
-def _confidence_args(who, confidence, confidence_scale):
-    """(token confidence wanted?, confidence_scale) of the confidence options of the two CTC decoders; refused before the model is
-    touched"""
-    confidence_scale = float(confidence_scale)
-    if not (math.isfinite(confidence_scale) and confidence_scale > 0.0):
-        raise ValueError(f"{who}: confidence_scale {confidence_scale} not finite and above 0")
-    if not confidence and confidence_scale != 1.0:
-        raise ValueError(f"{who}: confidence_scale {confidence_scale} without confidence=True (it scales the posterior of the votes)")
-    return bool(confidence), confidence_scale
-
-
-def _confidence_parts(parts, ids, n, score, N, order, n_best, scale, Lp, L):
-    """adds "token_confidence" f32 [B * n_best, L] (0 behind each row's length) and "confidence" f32 [B * n_best] to `parts`: the
-    votes of the whole list of N slots (js2t_nbest_confidence) for the tokens of the returned rows, order[:, :n_best]"""
-    B = order.shape[0]
-    _, conf, hyp = ops.nbest_confidence(ids, n, score.reshape(B * N), N, order[:, :n_best].contiguous(), scale, Lp=Lp)
-    conf = conf.reshape(B * n_best, Lp - 1).cpu().numpy()
-    tok = np.zeros((B * n_best, L), dtype=np.float32)
-    tok[:, :min(L, Lp - 1)] = conf[:, :L]
-    parts["token_confidence"], parts["confidence"] = tok, hyp.reshape(B * n_best).cpu().numpy()
-
-
-def _map_rank(order, B, N, dev):
-    """i64 [B, N]: the rank of every slot by the model score - the inverse of the last stage's `order`; None: the list came best
-    first, the rank of a slot is the slot"""
-    slots = torch.arange(N, device=dev, dtype=torch.int64).expand(B, N)
-    return slots if order is None else torch.empty((B, N), dtype=torch.int64, device=dev).scatter_(1, order.to(torch.int64), slots)
-
-
-def _ctc_first_pass(model, batch, who, beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=False, context=None,
-                    context_weight=0.0):
-    """The first pass of the two CTC decoders (inside their no_grad): encode once, project, pick the candidates of every frame and
-    search for the N best prefixes (blank = BOS) - `fused`: with the LM in the beam (ops.ctc_beam_search_lm over the model's
-    vocabulary, the lm moved to the device if need be); with a `context` graph: always ops.ctc_beam_search_ctx, the LM taking part
-    in it only when fused.  Returns (ids i64 [B, N, T], n i32 [B, N], ctc f32 [B, N] the pure CTC score, score f32 [B, N] the
-    search's own: ctc itself unless fused or biased, (B, T, V), [encoder output, its mask] with want_encoder, the context counts
-    i32 [B, N] or None without a graph)."""
-    from joeys2t_amd.alignment import _ctc_frames
-    ctc_out, _, in_len, *enc = _ctc_frames(model, batch, who=who, want_lse=False, want_encoder=want_encoder)
-    B, T, V = ctc_out.shape
-    logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-    cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
-    if not fused and context is None:
-        ids, n, ctc = ops.ctc_beam_search(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
-        return ids, n, ctc, ctc, (B, T, V), enc, None
-    if fused and lm is not None and lm.device != logits.device:
-        lm.to(logits.device)
-    if context is None:
-        ids, n, score, ctc, _ = ops.ctc_beam_search_lm(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index, lm,
-                                                       model.bos_index, model.eos_index, lm_weight, length_bonus)
-        return ids, n, ctc, score, (B, T, V), enc, None
-    if context.device != logits.device:
-        context.to(logits.device)
-    in_beam = (lm, lm_weight, length_bonus) if fused else (None, 0.0, 0.0)  # lm_fusion="rescore": the LM stays behind the search
-    ids, n, score, ctc, _, ctx = ops.ctc_beam_search_ctx(logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index,
-                                                         in_beam[0], model.bos_index, model.eos_index, in_beam[1], in_beam[2], context,
-                                                         context_weight)
-    return ids, n, ctc, score, (B, T, V), enc, ctx
-
-
-def _first_rows(order, n_best, N):
-    """(rows [B * n_best] into the flat [B * N] list, slots i64 [B, n_best]) of the n_best first of every utterance by `order`"""
-    slot = order[:, :n_best].to(torch.int64)
-    B = order.shape[0]
-    return (slot + torch.arange(B, device=order.device)[:, None] * N).reshape(B * n_best), slot
-
-
-def _nbest_numpy(ids, n, score):
-    """The decoders' return layout from device rows ids [R, T] (any leading shape), n [R], score [R]: NumPy ids i64 [R, L] cut to the
-    longest hypothesis (L at least 1), scores f32 [R, 1], lengths i64 [R]"""
-    n = n.cpu().numpy().astype(np.int64).reshape(-1)
-    L = max(int(n.max()) if n.size else 0, 1)
-    return np.ascontiguousarray(ids.cpu().numpy().reshape(n.size, ids.shape[-1])[:, :L]), score.cpu().numpy().reshape(n.size, 1), n
-
-
-def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
-                    length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore", decision: str = "map",
-                    mbr_scale: float = 1.0, return_parts: bool = False, confidence: bool = False, confidence_scale: float = 1.0,
-                    context=None, context_weight: float = 0.0):
-    """CTC prefix beam search over the encoder-side output layer alone (EXTENSION; no decoder runs): encode once, project with
-    `decoder.ctc_output_layer`, pick the `candidates` (<= 8) most probable labels of every frame and search over them with a beam of
-    `beam_size` (<= 32) prefixes, summing over all alignments of a prefix (js2t_ctc_beam_search; blank = BOS, model.py:84).
-    Returns NumPy in the row layout of `beam_search`: ids i64 [B * n_best, L] pad-filled (L = the longest hypothesis, at least 1),
-    scores f32 [B * n_best, 1] (log-probability of the labelling under the truncated distribution; -inf with an all-pad row where
-    an utterance has fewer than n_best prefixes) and lengths i64 [B * n_best].
-    With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus`, the `n_rescore` (default:
-    beam_size) best prefixes are searched for, re-ranked on the device by ctc + lm_weight * lm + length_bonus * n, lm = the LM's
-    log-probability of the labels and of EOS behind them (js2t_ngram_rescore), and the n_best first are returned with that score;
-    there is no host read between the encoder and the final copy.  Without either the search runs as it always did.
-    lm_fusion="search" applies the LM and the bonus INSIDE the beam instead (shallow fusion, js2t_ctc_beam_search_lm): every frame
-    prunes by ctc + lm_weight * lm + length_bonus * n, so a labelling the LM prefers survives where the CTC score alone would have
-    dropped it; the returned scores are the kernel's final scores (EOS term included).  There is no list to re-rank: n_rescore is
-    refused.
-    decision="mbr" (default "map": everything above) returns the minimum-Bayes-risk choice instead of the best-scored one: the
-    `n_rescore` (default: beam_size) best are searched for and scored exactly as above - n_rescore is then accepted without an LM
-    too, and with lm_fusion="search", where it is the fused search's n_best - and ranked on the device by their expected edit
-    distance to the list under the posterior softmax(mbr_scale * score) (js2t_mbr_rescore); the n_best first are returned.  The rows
-    of an utterance are then in ASCENDING RISK, not in descending score; the scores column keeps each row's model score, the value
-    the row would carry with decision="map".  Still no host read before the final copy.  A hypothesis of more than
-    ops.edit_max_len() labels takes no part (it is ranked last).
-    return_parts: a fourth element, a dict of per-returned-row NumPy data: "map_rank" i64 [B * n_best] (the row's rank within its
-    utterance by the model score) and, with decision="mbr", "risk" and "posterior" f32 [B * n_best].
-    context / context_weight (contextual biasing: a joeys2t_amd.biasing.ContextGraph of phrases that matter for this batch, and the
-    boost per matched token): with a graph and a non-zero weight the search is js2t_ctc_beam_search_ctx - every frame prunes by
-    ctc + context_weight * m, m = the tokens of the prefix inside completed phrases or the partial match at its end, and the final
-    score counts completed phrases only.  Biasing acts inside the beam, always: there is no "rescore" mode for it.  The LM and the
-    bonus take part in that kernel only under lm_fusion="search"; under "rescore" they re-rank the biased list, the kernel's final
-    score being the base of the n-gram stage.  Biasing adds no candidates: a phrase token that is not among a frame's `candidates`
-    (<= 8) best labels is still not proposed.  return_parts gains "context" i32 [B * n_best], the matched tokens of every row.  A
-    weight that is not finite, or non-zero without a graph, is refused before the model is touched.
-    confidence=True (token confidence from the list, js2t_nbest_confidence): the list of `n_rescore` (default: beam_size) slots is
-    searched for and scored exactly as with decision="mbr" - n_rescore is accepted without an LM, and under lm_fusion="search" it is
-    the fused search's n_best - the ranking stays whatever `decision` says, and every token of the returned rows gets the posterior
-    mass, under softmax(confidence_scale * score), of the list entries whose Levenshtein alignment with the row matches it.  The
-    call then returns the parts dict as with return_parts=True, with two more entries: "token_confidence" f32 [B * n_best, L], 0
-    behind each row's length, and "confidence" f32 [B * n_best], the row's own posterior.  Ids, scores and lengths are those of the
-    same call without it; still no host read before the final copy.  It says how much of the LIST's mass agrees with a token: it is
-    no calibrated probability.  A scale that is not finite or not above 0, or one other than 1 without confidence=True, is refused
-    before the model is touched."""
-    rerank, lm_weight, length_bonus = _ngram_args("ctc_beam_search", lm, lm_weight, length_bonus)
-    biased, context_weight = _context_args("ctc_beam_search", context, context_weight)
-    fused = _lm_fusion_arg("ctc_beam_search", lm_fusion, rerank)
-    mbr, mbr_scale = _decision_args("ctc_beam_search", decision, mbr_scale)
-    confidence, confidence_scale = _confidence_args("ctc_beam_search", confidence, confidence_scale)
-    wide = mbr or confidence  # the whole list of n_rescore slots is wanted, not the n_best first alone
-    return_parts = return_parts or confidence
-    if not 1 <= n_best <= beam_size:
-        raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
-    if fused and not wide:
-        if n_rescore is not None:
-            raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
-    elif rerank or wide:
-        n_rescore = int(beam_size if n_rescore is None else n_rescore)
-        if not n_best <= n_rescore <= beam_size:
-            raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
-    elif n_rescore is not None:
-        raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
-    beam_size, n_best = int(beam_size), int(n_best)
-    N = n_rescore if wide or (rerank and not fused) else n_best  # the slots searched for
-    with torch.no_grad():
-        ids, n, ctc, score, (B, T, _), _, ctx = _ctc_first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, fused, lm, lm_weight,
-                                                                length_bonus, context=context if biased else None,
-                                                                context_weight=context_weight)
-        order = None  # (the search returns its list best first)
-        if rerank and not fused:  # the N best re-ranked by the n-gram LM and the length bonus, the n_best first of them returned
-            # the base is the search's own score: the CTC score, with the context term when the search was biased; Lp = T + 1: no length to read
-            _, _, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, ids.device)
-        map_rank = _map_rank(order, B, N, ids.device) if return_parts else None
-        if mbr:  # the list ranked by its expected edit distance instead; Lp from the table's width: no length to read
-            _, posterior, risk, order = ops.mbr_rescore(ids, n, score.reshape(B * N), N, mbr_scale, Lp=min(T, ops.edit_max_len()) + 1)
-        if confidence and order is None:  # the list as the search left it: the returned rows are its first slots
-            order = torch.arange(N, device=ids.device, dtype=torch.int32).expand(B, N)
-        full = (ids, n, score)
-        if order is not None:
-            rows, _ = _first_rows(order, n_best, N)
-            ids, n, score = ids.view(B * N, T)[rows], n.view(B * N)[rows], score.reshape(B * N)[rows]
-        if not return_parts:
-            return _nbest_numpy(ids, n, score)
-        parts = {"map_rank": (map_rank.reshape(B * N)[rows] if order is not None else map_rank.reshape(B * N)).cpu().numpy()}
-        if mbr:
-            parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
-        if biased:
-            parts["context"] = (ctx.reshape(B * N)[rows] if order is not None else ctx.reshape(B * N)).cpu().numpy()
-        out = _nbest_numpy(ids, n, score)
-        if confidence:  # Lp from the table's width, as the MBR stage's: no length to read
-            _confidence_parts(parts, *full, N, order, n_best, confidence_scale, min(T, ops.edit_max_len()) + 1, out[0].shape[1])
-    return (*out, parts)
-
-
-def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,
-                          n_rescore: int = None, return_parts: bool = False, lm=None, lm_weight: float = 0.0,
-                          length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0,
-                          confidence: bool = False, confidence_scale: float = 1.0, context=None, context_weight: float = 0.0):
-    """Two-pass decoding (EXTENSION; the reference has no consumer of ctc_out): the `n_rescore` (default: beam_size) best hypotheses
-    of CTC prefix beam search (`ctc_beam_search`: beam_size, candidates) are scored by the attention decoder in ONE teacher-forced pass
-    over B * n_rescore rows - no step loop - and re-ranked by ctc_weight * ctc + (1 - ctc_weight) * attention, attention = the sum of
-    the log-probabilities of the hypothesis' labels and of EOS behind them (js2t_rescore).  The encoder runs once; the n-best list,
-    the decoder input and the scores stay on the device, with one host read (the longest hypothesis) to size the decoder pass.
-    The decoder input is [BOS, labels...] with the target mask made from the LENGTHS (a hypothesis may contain pad or EOS as labels);
-    the encoder output and its mask are tiled n_rescore times as `beam_search` does - the padded path: packed encoder rows are not
-    handed to the decoder here.
-    Returns NumPy in `ctc_beam_search`'s layout: ids i64 [B * n_best, L] pad-filled, scores f32 [B * n_best, 1] (the combined score;
-    -inf with an all-pad row where an utterance has fewer than n_best prefixes), lengths i64 [B * n_best]; with return_parts a fourth
-    element, a dict of per-returned-row NumPy data: "ctc" and "attention" f32 [B * n_best] (the two scores), "token_log_probs" (a
-    list of f32 arrays of n + 1 values, the last one EOS's) and "ctc_rank" i64 [B * n_best] (the slot of the row in the CTC n-best).
-    With an `lm` (joeys2t_amd.lm.NGramLM over the target vocabulary) or a non-zero `length_bonus` the final score is
-    ctc_weight * ctc + (1 - ctc_weight) * attention + lm_weight * lm + length_bonus * n: js2t_rescore's combined score is the base
-    score of js2t_ngram_rescore, whose ranking decides; the parts gain "lm" f32 [B * n_best] and "lm_token_log_probs".
-    lm_fusion="search": the first pass is the LM-fused beam search (js2t_ctc_beam_search_lm with n_best = n_rescore), so the list
-    that is re-scored already holds the labellings the LM prefers; its pure CTC score (out_ctc) is js2t_rescore's CTC score, the
-    rest is unchanged and "ctc_rank" is the slot in the fused list.
-    decision="mbr" (default "map": everything above): the n_rescore hypotheses are scored exactly as above and then ranked on the
-    device by their expected edit distance to the list under the posterior softmax(mbr_scale * final score) (js2t_mbr_rescore); the
-    n_best first are returned.  The rows of an utterance are then in ASCENDING RISK, not in descending score; the scores column keeps
-    each row's final model score.  The parts gain "risk" and "posterior" f32 [B * n_best] and "map_rank" i64 [B * n_best], the row's
-    rank within its utterance by the final model score.  The host read that sizes the decoder pass stays the only one.
-    context / context_weight (contextual biasing, `ctc_beam_search`): with a graph and a non-zero weight the first pass is the biased
-    search (js2t_ctc_beam_search_ctx with n_best = n_rescore; the LM in it only under lm_fusion="search"), so the list that is
-    re-scored holds the labellings the phrases keep alive.  js2t_rescore takes the pure CTC score as ever; the context term,
-    context_weight * the matched tokens of completed phrases, is added behind the n-gram stage and in front of the MBR decision
-    (js2t_context_rescore), and its ranking decides.  The parts gain "context" i32 [B * n_best].  A weight that is not finite, or
-    non-zero without a graph, is refused before the model is touched.
-    confidence / confidence_scale (token confidence from the list, `ctc_beam_search`): the votes are those of the n_rescore
-    hypotheses under softmax(confidence_scale * final score), for the tokens of the returned rows, whatever `decision` ranked them
-    by; the call returns the parts with "token_confidence" f32 [B * n_best, L] and "confidence" f32 [B * n_best] added.  Ids, scores
-    and lengths are those of the same call without it."""
-    rerank, lm_weight, length_bonus = _ngram_args("ctc_attention_rescore", lm, lm_weight, length_bonus)
-    biased, context_weight = _context_args("ctc_attention_rescore", context, context_weight)
-    fused = _lm_fusion_arg("ctc_attention_rescore", lm_fusion, rerank)
-    mbr, mbr_scale = _decision_args("ctc_attention_rescore", decision, mbr_scale)
-    confidence, confidence_scale = _confidence_args("ctc_attention_rescore", confidence, confidence_scale)
-    return_parts = return_parts or confidence
-    n_rescore = beam_size if n_rescore is None else n_rescore
-    beam_size, n_best, n_rescore, ctc_weight = int(beam_size), int(n_best), int(n_rescore), float(ctc_weight)
-    if not 1 <= n_best <= n_rescore <= beam_size <= 32:
-        raise ValueError(f"ctc_attention_rescore: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} <= 32 expected "
-                         "(all at least 1)")
-    if not 0.0 <= ctc_weight <= 1.0:  # (a NaN fails too)
-        raise ValueError(f"ctc_attention_rescore: ctc_weight {ctc_weight} outside [0, 1]")
-    N = n_rescore
-    with torch.no_grad():
-        ids, n, ctc, _, (B, T, _), (encoder_output, src_mask), _ = _ctc_first_pass(
-            model, batch, "ctc_attention_rescore", beam_size, N, candidates, fused, lm, lm_weight, length_bonus, want_encoder=True,
-            context=context if biased else None, context_weight=context_weight)
-        dev = ids.device
-        Lp = int(n.max().item()) + 1 if n.numel() else 1  # the one host read: it sizes the decoder pass
-        ids2 = ids.view(B * N, T)
-        trg_input = torch.cat([torch.full((B * N, 1), model.bos_index, dtype=torch.int64, device=dev), ids2[:, :Lp - 1]], dim=1).contiguous()
-        trg_mask = (torch.arange(Lp, device=dev)[None, :] <= n.view(B * N, 1)).unsqueeze(1)  # [R, 1, Lp] from the lengths, not from pad ids
-        dec_logits, _, _, _ = model(return_type="decode", trg_input=trg_input, encoder_output=tile(encoder_output.contiguous(), N, dim=0),
-                                    encoder_hidden=None, src_mask=tile(src_mask, N, dim=0), unroll_steps=None, decoder_hidden=None,
-                                    trg_mask=trg_mask)
-        tok_lp, att, score, order = ops.rescore(dec_logits.contiguous(), ids, n, ctc, N, model.eos_index, ctc_weight)
-        if rerank:
-            lm_tok, lm_score, score, order = _ngram_rerank(model, ids, n, score, N, lm, lm_weight, length_bonus, dev, Lp=Lp,
-                                                           want_tokens=return_parts)
-        if biased:  # the context term on top of whatever the stages before it made of the list
-            ctx, score, order = ops.context_rescore(ids, n, score, N, context, context_weight, Lp=Lp)
-        if mbr:  # the same list and scores, ranked by the expected edit distance instead
-            map_rank = _map_rank(order, B, N, dev) if return_parts else None
-            _, posterior, risk, order = ops.mbr_rescore(ids, n, score, N, mbr_scale, Lp=Lp)
-        rows, slot = _first_rows(order, n_best, N)  # the n_best first of every utterance
-        out_ids, out_score, out_n = _nbest_numpy(ids2[rows], n.view(B * N)[rows], score[rows])
-        if not return_parts:
-            return out_ids, out_score, out_n
-        tl = tok_lp[rows].cpu().numpy()
-        parts = {"ctc": ctc.view(B * N)[rows].cpu().numpy(), "attention": att[rows].cpu().numpy(),
-                 "token_log_probs": [tl[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)],
-                 "ctc_rank": slot.reshape(B * n_best).cpu().numpy()}
-        if rerank:
-            ll = lm_tok[rows].cpu().numpy()
-            parts["lm"] = lm_score[rows].cpu().numpy()
-            parts["lm_token_log_probs"] = [ll[i, :int(out_n[i]) + 1].copy() for i in range(B * n_best)]
-        if mbr:
-            parts["risk"], parts["posterior"] = risk[rows].cpu().numpy(), posterior[rows].cpu().numpy()
-            parts["map_rank"] = map_rank.reshape(B * N)[rows].cpu().numpy()
-        if biased:
-            parts["context"] = ctx[rows].cpu().numpy()
-        if confidence:
-            _confidence_parts(parts, ids, n, score, N, order, n_best, confidence_scale, min(Lp, ops.edit_max_len() + 1), out_ids.shape[1])
-    return out_ids, out_score, out_n, parts
+# the decoders over the CTC output layer (EXTENSION: not part of the reference's surface) live in ctc_search.py
+from joeys2t_amd.ctc_search import ctc_attention_rescore, ctc_beam_search, ctc_greedy  # noqa: E402,F401
