@@ -923,6 +923,46 @@ int js2t_beam_step_logp(const float* log_probs, const float* beam_log_probs, flo
                         float* out_lse, int64_t n_batch, int32_t beam, int64_t V, const int32_t* forbid_ids,
                         int32_t n_forbid, float length_penalty, js2t_stream stream);
 
+/* EXTENSION (the reference has no sampling: its attention decoder takes the arg-max or runs a beam; the checker is a float64
+ * restatement of the rule below, tests/sampling_reference.py): one sampling step of the attention decoder - temperature, epsilon /
+ * top-k / nucleus truncation, renormalisation, the draw and the per-row state, one launch over [rows, V] logits, a block per row.
+ * Natural logarithms, f32.
+ * logits f32 [rows, V], rows ld >= 0 elements apart; neither the base nor ld need be 16-byte aligned: a view gives the bits of its
+ * contiguous copy.  u f32 [rows]: one uniform number per row, a NaN counts as 0, values are clamped into [0, 1).  forbid_ids: a HOST
+ * array of at most 16 ids (js2t_beam_step's), ids outside 0 .. V-1 are ignored.  ids i64: the table of drawn ids, row r at
+ * ids + r * ids_ld; only column `step` is written.  out_logp f32 [rows].  out_q f32 [rows], score f32 [rows], length i32 [rows],
+ * out_kept i32 [rows], out_cdf f32 [rows, 2] and finished u8 [rows] may each be NULL (no finished: every row is live).
+ * Row r:
+ *   finished row (finished[r] != 0): ids[r, step] = pad, out_logp = out_q = 0, out_kept = 0, out_cdf = (0, 0); score and length are
+ *     untouched; neither the row's logits nor its u are read.
+ *   live row: a NaN logit counts as -inf.  A = the ids that are not forbidden and whose logit is > -inf.  lse_all = log-sum-exp of the
+ *     WHOLE row, forbidden ids included: js2t_beam_step's normaliser, so scores equal the greedy path's.  +inf is not supported
+ *     input (it is carried as the largest finite value: the id returned is still in range and not forbidden).
+ *   A empty: id = eos, out_logp = -inf, out_q = 0, out_kept = 0, out_cdf = (0, 0); the row becomes finished.
+ *   order pi: A by RAW logit descending, id ascending among equals (temperature is monotone: every truncation is a prefix of pi).
+ *   masses: e_v = exp((logit_v - max_A logit) / temperature), q0_v = e_v / sum_A e;
+ *     n_eps = max(1, #{v in A: q0_v >= epsilon}); n_k = |A| if top_k == 0 else min(top_k, |A|); n0 = min(n_eps, n_k).
+ *   nucleus: top_p == 1 exactly: j = n0 (the term is left out); else j = the smallest count in 1 .. n0 with
+ *     sum_{i <= j} e_pi(i) >= top_p * sum_{i <= n0} e_pi(i) (renormalise, then nucleus).  Kept set K = the first j of pi; equal logits
+ *     across the boundary enter in id order.
+ *   draw: K in ASCENDING ID order, W = sum_K e, C_v the inclusive running sum: id = the smallest kept v with C_v > u * W (if
+ *     rounding leaves none: the largest kept id - never a dropped id, never out of range).
+ *   outputs: out_logp = logit_id - lse_all (the model's own log-probability, whatever the truncation); out_q = log(e_id / W) (under
+ *     the distribution drawn from); out_kept = j; out_cdf = ((C_id - e_id) / W, C_id / W).
+ *   state: ids[r, step] = id; finished[r] |= (id == eos); score[r] += out_logp (ONE f32 addition per step: the sum is in ascending
+ *     step order, the same bits alone and in a batch); length[r] += (id != eos).
+ * A row depends on its own logits and u only.  Masses are summed as 2^-40 fixed-point integers (e_v <= 1 truncated to 2^-40, at most
+ * V * 2^-40 of the total): exact, order-free sums - integer LDS atomics only, no floating-point atomics, no result that depends on
+ * thread scheduling, the same bits under graph replay.
+ * Limits, each refused before a launch: 2 <= V <= 65536, n_forbid <= 16, temperature finite and > 0, top_k >= 0 (values above V
+ * mean V), 0 < top_p <= 1, 0 <= epsilon < 1, 0 <= step < ids_ld, 0 <= eos, pad < V, 0 <= rows < 2^31, ld >= 0; rows = 0 returns 0
+ * without a launch.
+ * One launch on `stream`; no workspace, no allocation, no synchronisation: capturable. */
+int js2t_sample_step(const float* logits, int64_t ld, const float* u, uint8_t* finished, int64_t* ids, int64_t ids_ld, int32_t step,
+                     float* out_logp, float* out_q, float* score, int32_t* length, int32_t* out_kept, float* out_cdf, int64_t rows,
+                     int64_t V, const int32_t* forbid_ids, int32_t n_forbid, float temperature, int32_t top_k, float top_p,
+                     float epsilon, int64_t eos, int64_t pad, js2t_stream stream);
+
 /* EXTENSION (the reference returns ctc_out for return_type="decode_ctc", joeynmt/model.py:162-166, and has no
  * consumer): joint CTC / attention decoding after Watanabe et al., IEEE JSTSP 2017, Algorithm 2.
  * js2t_beam_pick: for every row of logits [rows, V] the n_pick (<= 8) best tokens by log-softmax (forbidden ids masked) +

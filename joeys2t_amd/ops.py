@@ -1240,6 +1240,49 @@ def beam_pick(logits2d: torch.Tensor, n_pick: int, forbid_ids, row_scores: Optio
     return scores, ids, lse
 
 
+SAMPLE_MAX_V = 65536  # js2t_sample_step's longest row
+
+
+def sample_step(logits2d: torch.Tensor, u: torch.Tensor, ids: torch.Tensor, step: int, forbid_ids, eos: int, pad: int, *,
+                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, epsilon: float = 0.0, finished=None, score=None,
+                length=None, out=None, want=("q", "kept", "cdf")):
+    """One sampling step of the attention decoder (js2t_sample_step): logits2d f32 [rows, V] with dense rows any number of elements
+    apart (a view at any storage offset is fine), u f32 [rows] uniform numbers, ids i64 [rows, width] the table whose column `step` is
+    written (rows dense, any distance apart).  State updated in place where given: finished u8 [rows], score f32 [rows] (+= the drawn
+    token's log-probability under the model), length i32 [rows] (+= 1 unless EOS was drawn).
+    Returns (out_logp f32 [rows], out_q f32 [rows] or None, out_kept i32 [rows] or None, out_cdf f32 [rows, 2] or None): `want` names
+    the optional three that are allocated; out = the four tensors to write instead (the optional ones may be None)."""
+    _dev(logits2d, u, ids, *(t for t in (finished, score, length, *(out or ())) if t is not None))
+    if logits2d.dim() != 2 or logits2d.dtype != torch.float32 or (logits2d.shape[1] > 1 and logits2d.stride(1) != 1) or logits2d.stride(0) < 0:
+        raise Js2tError(f"sample_step: f32 logits [rows, V] with dense rows expected, got {logits2d.dtype} {tuple(logits2d.shape)} "
+                        f"strides {logits2d.stride()}")
+    rows, V = logits2d.shape
+    if ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != rows or (ids.shape[1] > 1 and ids.stride(1) != 1) or ids.stride(0) < 0:
+        raise Js2tError(f"sample_step: ids = i64 [{rows}, width] with dense rows expected, got {ids.dtype} {tuple(ids.shape)} strides {ids.stride()}")
+    ids_ld = ids.stride(0) if rows > 1 else ids.shape[1]
+    if rows > 1 and 0 < ids_ld < ids.shape[1]:
+        raise Js2tError(f"sample_step: rows of ids {ids_ld} elements apart overlap at width {ids.shape[1]}")
+    if not 0 <= int(step) < ids.shape[1]:
+        raise Js2tError(f"sample_step: step {step} outside 0 .. {ids.shape[1] - 1}")
+    for name, t, dt in (("u", u, torch.float32), ("finished", finished, torch.uint8), ("score", score, torch.float32),
+                        ("length", length, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != rows or not t.is_contiguous()):
+            raise Js2tError(f"sample_step: {name} = contiguous {_DT_NAME[dt]} [{rows}] expected, got {t.dtype} {tuple(t.shape)}")
+    if u is None:
+        raise Js2tError("sample_step: u = contiguous f32 [rows] expected, got None")
+    if len(forbid_ids) > 16:
+        raise Js2tError(f"sample_step: {len(forbid_ids)} forbidden ids, at most 16")
+    absent = tuple(k for k, name in ((1, "q"), (2, "kept"), (3, "cdf")) if name not in want)
+    logp, q, kept, cdf = _nbest_out("sample_step", out, (((rows, ), torch.float32), ((rows, ), torch.float32), ((rows, ), torch.int32),
+                                                         ((rows, 2), torch.float32)), logits2d.device, optional=(1, 2, 3), absent=absent)
+    fb = (C.c_int32 * max(1, len(forbid_ids)))(*[int(i) for i in forbid_ids])
+    ld = logits2d.stride(0) if rows > 1 else V
+    check(lib().js2t_sample_step(_p(logits2d), ld, _p(u), _p(finished), _p(ids), ids_ld, int(step), _p(logp), _p(q), _p(score), _p(length),
+                                 _p(kept), _p(cdf), rows, V, fb, len(forbid_ids), float(temperature), int(top_k), float(top_p),
+                                 float(epsilon), int(eos), int(pad), _stream()), "js2t_sample_step")
+    return logp, q, kept, cdf
+
+
 CTC_LOG0 = -1.0e30  # log 0 of the CTC prefix variables (js2t_ctc_prefix_step carries no infinities)
 
 

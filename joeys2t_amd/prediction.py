@@ -22,6 +22,7 @@ from joeys2t_amd.helpers import expand_reverse_index
 from joeys2t_amd.helpers_for_ddp import ddp_merge, ddp_reduce, use_ddp
 from joeys2t_amd.ctc_search import (confidence_args, context_args, ctc_attention_rescore, ctc_beam_search, decision_args, lm_fusion_arg,
                                      lm_given)
+from joeys2t_amd.sampling import MBR_MAX_SAMPLES, sample_args, sample_search
 from joeys2t_amd.search import search
 
 
@@ -31,7 +32,8 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             return_attention: bool = False, compute_loss: bool = False, normalization: str = "batch", n_gpu: int = 1,
             decoder: str = "attention", ctc_candidates: int = 8, ctc_weight: float = 0.3, lm=None, lm_weight: float = 0.0,
             length_bonus: float = 0.0, lm_fusion: str = "rescore", decision: str = "map", mbr_scale: float = 1.0,
-            confidence: bool = False, confidence_scale: float = 1.0, context=None, context_weight: float = 0.0):
+            confidence: bool = False, confidence_scale: float = 1.0, n_samples: int = 1, temperature: float = 1.0, top_k: int = 0,
+            top_p: float = 1.0, epsilon: float = 0.0, seed: int = 0, context=None, context_weight: float = 0.0):
     """Returns (id arrays in the ORIGINAL batch order, decoded token lists, scores or None); with `return_attention` a fourth
     element: the attention arrays of greedy search (prediction.py:205-218 hands the same options to `search`, which derives
     `encoder_input` / the forced prefix from the batch); with `compute_loss` a last element, the validation record
@@ -61,9 +63,22 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
     tokens' confidences, in the original order of the ids], "hypothesis": np.float32 array, each hypothesis' own posterior}.  It
     says how much of the list's mass agrees with a token; it is no calibrated probability.  The attention decoder has no such list
     and refuses them, return_prob="ref" runs no search and refuses them, and under a process group confidence=True is refused:
-    merging ragged per-token arrays across ranks is out of scope here."""
-    if decoder not in ("attention", "ctc", "ctc-attention"):
-        raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention'")
+    merging ragged per-token arrays across ranks is out of scope here.
+    decoder="sample" (EXTENSION) / n_samples, temperature, top_k, top_p, epsilon, seed: `search.sample_search` - n_samples draws per
+    sentence from the attention decoder under temperature / top-k / nucleus / epsilon truncation, from ONE device generator seeded
+    with `seed` and carried across the batches.  decision="map" (the default) returns the draws in draw order and needs n_best ==
+    n_samples; decision="mbr" returns the n_best draws of smallest expected edit distance to the sentence's draws (sampled MBR, uniform
+    posterior: mbr_scale has nothing to scale).  Scores (return_prob="hyp") are the draws' log-probabilities under the model.  The
+    options of the other decoders (lm*, lm_fusion, context*, confidence*, ctc_*, beam_alpha, repetition_penalty, no_repeat_ngram_size,
+    return_attention) are refused, the six sampling options are refused with any other decoder unless at their defaults, and under a
+    process group the decoder is refused: merging is out of scope, as for confidence."""
+    if decoder not in ("attention", "ctc", "ctc-attention", "sample"):
+        raise ValueError(f"predict: decoder '{decoder}' is none of 'attention', 'ctc', 'ctc-attention', 'sample'")
+    sample = decoder == "sample"
+    n_samples, temperature, top_k, top_p, epsilon = sample_args("predict", n_samples, temperature, top_k, top_p, epsilon)
+    if not sample and (n_samples, temperature, top_k, top_p, epsilon, int(seed)) != (1, 1.0, 0, 1.0, 0.0, 0):
+        raise ValueError(f"predict: n_samples / temperature / top_k / top_p / epsilon / seed belong to decoder='sample', not to "
+                         f"decoder='{decoder}'")
     if decoder == "attention" and lm_given(lm, lm_weight, length_bonus):
         raise ValueError("predict: lm / lm_weight / length_bonus re-rank the n-best list of decoder='ctc' or 'ctc-attention'; "
                          "decoder='attention' cannot apply them")
@@ -85,6 +100,25 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
         raise ValueError("predict: confidence=True with return_prob='ref' (no search runs: there is no n-best list to vote)")
     if confidence and use_ddp():
         raise ValueError("predict: confidence=True under a process group (per-token arrays are not merged across ranks)")
+    if sample:
+        other = {"lm / lm_weight / length_bonus": lm_given(lm, lm_weight, length_bonus), "lm_fusion": lm_fusion != "rescore",
+                 "context / context_weight": context is not None or biased, "confidence": confidence,
+                 "ctc_candidates / ctc_weight": ctc_candidates != 8 or ctc_weight != 0.3, "beam_alpha": beam_alpha != -1.0,
+                 "mbr_scale": mbr_scale != 1.0, "repetition_penalty": repetition_penalty != -1,
+                 "no_repeat_ngram_size": no_repeat_ngram_size != -1, "return_attention": bool(return_attention)}
+        for name, given in other.items():
+            if given:
+                raise ValueError(f"predict: {name} belongs to another decoder; decoder='sample' draws from the attention decoder and "
+                                 f"has no place for it")
+        if not mbr and n_best != n_samples:
+            raise ValueError(f"predict: decoder='sample' with decision='map' returns the draws in draw order: n_best {n_best} must equal "
+                             f"n_samples {n_samples}")
+        if mbr and not (2 <= n_samples <= MBR_MAX_SAMPLES and 1 <= n_best <= n_samples):
+            raise ValueError(f"predict: decoder='sample' with decision='mbr' ranks 2..{MBR_MAX_SAMPLES} samples and returns 1..n_samples "
+                             f"of them, got n_samples {n_samples}, n_best {n_best}")
+        if use_ddp():
+            raise ValueError("predict: decoder='sample' under a process group (the draws are not merged across ranks)")
+    sample_gen = None
     lm_kw = {} if not lm_given(lm, lm_weight, length_bonus) else \
         dict(lm=lm, lm_weight=lm_weight, length_bonus=length_bonus)  # nothing given: the decoders are called as they always were
     if lm_fusion != "rescore":
@@ -129,6 +163,15 @@ def predict(model, batches: Iterable[Batch], *, beam_size: int = 1, beam_alpha: 
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref" and ctc:
             ids, scores, lens, *parts = ctc_beam_search(model, batch, beam_size=beam_size, n_best=n_best, candidates=ctc_candidates, **lm_kw)
+            scores = scores if return_prob == "hyp" else None
+        elif return_prob != "ref" and sample:
+            if sample_gen is None:  # one generator for all batches: a later batch continues the stream
+                sample_gen = torch.Generator(device=device)
+                sample_gen.manual_seed(int(seed))
+            ids, scores, lens = sample_search(model, batch, n_samples=n_samples, max_output_length=max_output_length,
+                                              min_output_length=min_output_length, temperature=temperature, top_k=top_k, top_p=top_p,
+                                              epsilon=epsilon, generate_unk=generate_unk, decision="mbr" if mbr else "none", n_best=n_best,
+                                              generator=sample_gen)
             scores = scores if return_prob == "hyp" else None
         elif return_prob != "ref":
             ids, scores, att = search(model=model, batch=batch, beam_size=beam_size, beam_alpha=beam_alpha, n_best=n_best,

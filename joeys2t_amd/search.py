@@ -470,3 +470,5 @@ def search(model, batch, max_output_length: int, beam_size: int, beam_alpha: flo
 
 # the decoders over the CTC output layer (EXTENSION: not part of the reference's surface) live in ctc_search.py
 from joeys2t_amd.ctc_search import ctc_attention_rescore, ctc_beam_search, ctc_greedy  # noqa: E402,F401
+# sampling from the attention decoder (EXTENSION) lives in sampling.py
+from joeys2t_amd.sampling import sample_search  # noqa: E402,F401
