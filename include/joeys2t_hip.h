@@ -646,6 +646,58 @@ int js2t_context_walk_host(const int64_t* ids, int64_t n, const void* ctx_nodes,
                            int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail, int64_t V, int32_t* out_node,
                            int32_t* out_bank, int32_t* out_m, int32_t* out_ctx);
 
+/* EXTENSION (the reference decodes utterances; nothing in it takes a recording): long-form CTC.  A recording is encoded as W
+ * overlapping windows of S encoder frames; the frames near a window's edge lack context, so only a centre range of every window is
+ * kept and the kept ranges, back to back, are one frame-synchronous posterior stream.  js2t_ctc_segment cuts that stream where the
+ * model itself says nothing is spoken, and the segments - packed rows with offsets - go to the CTC kernels above as a ragged batch.
+ *
+ * js2t_ctc_stitch.  logits [W, S, V] f32 or bf16.  keep_lo / keep_hi / out_row i32 [W]: window w keeps its frames keep_lo[w] ..
+ * keep_hi[w] - 1 (0 <= lo <= hi <= S; lo == hi keeps nothing) and frame j of it becomes row out_row[w] + j - keep_lo[w] of the
+ * outputs.  Per kept frame, its logits read from memory ONCE:
+ *   out[row, :] f32 [rows, V] = the logits (bf16 widened, f32 copied bit for bit) - the layout row_offsets consumers read;
+ *   lse[row]; argmax[row] i64 = the first index of the maximum; blank_lp[row] = out[row, blank] - lse[row].
+ * lse and argmax have the BITS js2t_row_lse gives for out[row, :]: one reduction in one order (csrc/row_lse.hpp), f32, no atomics -
+ * the same alone, in a batch and under graph replay.  One wave per row up to V = 1024, one block per row above; 128-bit loads and
+ * stores on the 16-byte aligned body of a row, scalar head and tail (source and destination rows may be aligned differently).
+ * Nothing outside a kept range is read; rows no window writes keep their contents.  The arrays are read on the device and cannot be
+ * refused: a range is clamped to 0 .. S and a frame whose row lies outside 0 .. rows - 1 is skipped; rows written by two windows are
+ * the caller's error (the result is one of the two).
+ * Limits: 1 <= V <= 12000 (a row is staged in LDS, inside 48 KB), 0 <= blank < V, W <= 65535, S and rows below 2^31; W, S or rows = 0
+ * returns 0.  MEMORY: the stitched stream is rows * V * 4 bytes - an hour at 25 frames per second and V = 10000 is 3.6 GB; what an hour
+ * costs end to end has not been measured.  One launch; no allocation, no synchronisation: capturable. */
+int js2t_ctc_stitch(const void* logits, int dt, const int32_t* keep_lo, const int32_t* keep_hi, const int32_t* out_row, float* out,
+                    float* lse, int64_t* argmax, float* blank_lp, int64_t W, int64_t S, int64_t V, int64_t rows, int64_t blank,
+                    js2t_stream stream);
+
+/* js2t_ctc_segment.  blank_lp f32 [T] and argmax i64 [T] of ONE recording (js2t_ctc_stitch's); all lengths in encoder frames.
+ * The rule (part of the contract; tests/long_form_reference.py restates it in Python):
+ *   - frame t is SILENT iff argmax[t] == blank and blank_lp[t] >= log_threshold (a NaN blank_lp: not silent);
+ *   - a PAUSE is a maximal run of silent frames of at least min_silence frames; the speech REGIONS are the non-empty stretches
+ *     between pauses, before the first and behind the last one - so a pause that opens or closes the recording is dropped;
+ *   - a region [a, b) is WIDENED to [a', b'): a' = max(a - margin, lim), lim = 0 if no pause lies in front or that pause opens the
+ *     recording, else the midpoint s + (e - s) / 2 of that pause [s, e); b' = min(b + margin, lim), lim = T if no pause lies behind
+ *     or it closes the recording, else that pause's midpoint (integer division; both neighbours clamp to the same midpoint, so regions
+ *     never overlap, and they touch when 2 * margin covers the pause);
+ *   - a widened region is CUT greedily from the left into pieces [start, c): while b' - start > max_len, c is the largest cut in
+ *     (start + max_len / 2, start + max_len] whose frame c - 1 is silent - the cut falls behind the last silent frame of the upper
+ *     half - or start + max_len if there is none; the rest is the last piece;
+ *   - a piece of silent frames only is dropped (an uncut region is one piece); every other piece is a segment.
+ * Outputs: n_seg i32 [1]; seg_off i32 [max_segments + 1], ascending, seg_off[i] the first frame of segment i and seg_off[n_seg] one
+ * past the end of the last one (0 without segments): row_offsets as the CTC kernels read them; seg_len i64 [max_segments] the
+ * lengths, the kernels' in_len - with a margin the segments need not touch, so the offsets alone do not give them.  More than
+ * max_segments segments: n_seg = -1 and nothing else is written.  There are at most T / min_silence + T / (max_len / 2 + 1) + 2
+ * segments (a forced piece is longer than max_len / 2).
+ * workspace: js2t_ctc_segment_workspace_bytes(T) bytes, 4-byte aligned, contents on entry do not matter.
+ * One block: the silent bits and "the last frame in the other state" by ballot and a scan over waves, the pauses compacted in order,
+ * then one wave with a lane per region that walks its cuts twice - counting, then writing behind a prefix sum.  No atomics: the same
+ * bits on every run and under graph replay.
+ * Limits: 0 <= T < 2^30 (T = 0: n_seg = 0), 1 <= min_silence, 0 <= margin, 1 <= max_len, 0 <= max_segments, log_threshold not NaN.
+ * No allocation, no synchronisation: capturable. */
+int64_t js2t_ctc_segment_workspace_bytes(int64_t T);
+int js2t_ctc_segment(const float* blank_lp, const int64_t* argmax, int64_t T, int64_t blank, float log_threshold, int32_t min_silence,
+                     int32_t margin, int32_t max_len, int32_t max_segments, int32_t* n_seg, int32_t* seg_off, int64_t* seg_len,
+                     void* workspace, js2t_stream stream);
+
 /* EXTENSION (the reference has no edit distance on the device): unit-cost Levenshtein distances of pairs of rows of i64 ids, one wave
  * per pair.  Row r of `a` lies at a + r * a_stride and has a_len[r] (i32) ids; it is compared with row r / group of `b`, at
  * b + (r / group) * b_stride with b_len[r / group] ids: group = 1 pairs the rows one to one, group = N compares the N hypotheses of an

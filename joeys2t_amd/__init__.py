@@ -4,3 +4,14 @@ Everything numeric runs in hand-written HIP kernels for gfx950 (libjoeys2t_hip.s
 include/joeys2t_hip.h).  PyTorch provides device memory, streams, autograd routing and torch.distributed.
 """
 __version__ = "0.1.0"
+
+_LONG_FORM = ("plan_windows", "stitch_posteriors", "segment", "decode_stream", "transcribe_long")  # joeys2t_amd.long_form: one recording to text
+__all__ = ["long_form", *_LONG_FORM]
+
+
+def __getattr__(name):  # on first use: importing the package stays free of torch and of the library
+    if name == "long_form" or name in _LONG_FORM:
+        import importlib
+        module = importlib.import_module("joeys2t_amd.long_form")
+        return module if name == "long_form" else getattr(module, name)
+    raise AttributeError(f"module 'joeys2t_amd' has no attribute '{name}'")

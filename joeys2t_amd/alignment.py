@@ -71,15 +71,25 @@ def forced_align(model, batch, trg=None, trg_length=None, frame_shift_ms: float 
             raise ValueError(f"forced_align: targets [B, L] and lengths [B] for B = {ctc_out.shape[0]} expected, got "
                              f"{tuple(trg.shape)} and {tuple(trg_length.shape)}")
         path, tok_start, tok_end, frame_logp, score = ops.ctc_align(ctc_out, lse, trg, in_len, trg_length, int(model.bos_index))
-        tok_start, tok_end, frame_logp, score = (t.cpu().numpy() for t in (tok_start, tok_end, frame_logp, score))
-        trg_h, len_h = trg.cpu().numpy(), np.minimum(trg_length.cpu().numpy(), trg.shape[1])
-    sec = frame_seconds(model, frame_shift_ms)
+        return alignments(trg.cpu().numpy(), trg_length.cpu().numpy(), tok_start, tok_end, frame_logp, score, frame_seconds(model, frame_shift_ms))
+
+
+def alignments(trg_h, len_h, tok_start, tok_end, frame_logp, score, sec: float, first_frame=None) -> List[Alignment]:
+    """js2t_ctc_align's outputs as one Alignment per utterance.  trg_h [B, L] / len_h [B]: the labels on the host; first_frame
+    (optional, [B]): where each utterance begins in a longer recording - its frames and seconds are then counted from there
+    (long_form.transcribe_long's segments; frame_logp stays indexed from the utterance's own first frame)."""
+    tok_start, tok_end, frame_logp, score = (t.cpu().numpy() for t in (tok_start, tok_end, frame_logp, score))
+    trg_h = np.asarray(trg_h)
+    len_h = np.minimum(np.asarray(len_h), trg_h.shape[1])
     out = []
     for b in range(trg_h.shape[0]):
         L = max(int(len_h[b]), 0)
+        f0 = 0 if first_frame is None else int(first_frame[b])
         s, e = tok_start[b, :L].tolist(), tok_end[b, :L].tolist()
         ok = np.isfinite(score[b])
         logp = [float(np.mean(frame_logp[b, i:j], dtype=np.float64)) if ok else float("nan") for i, j in zip(s, e)]
+        if ok:
+            s, e = [i + f0 for i in s], [j + f0 for j in e]
         out.append(Alignment(tokens=trg_h[b, :L].tolist(), start_frame=s, end_frame=e, start=[i * sec if ok else float("nan") for i in s],
                              end=[j * sec if ok else float("nan") for j in e], logp=logp, score=float(score[b])))
     return out

@@ -3,10 +3,11 @@
 // recursions in log space and the CTC gradient w.r.t. the logits, plus small deterministic reductions.
 // All HBM-bound: one pass over the logits per kernel, wavefront-shuffle + LDS block reductions.
 #include "common.hpp"
+#include "row_lse.hpp"
 
 namespace {
 
-constexpr int LB = 256;  // threads per row-block
+constexpr int LB = ROW_LSE_THREADS;  // threads per row-block
 
 __device__ __forceinline__ float logaddexp(float a, float b) {
   if (a == -INFINITY) return b;
@@ -29,34 +30,17 @@ __device__ __forceinline__ float logaddexp_fast(float a, float b) {
 template <typename T>
 __global__ __launch_bounds__(LB) void row_lse_kernel(const T* __restrict__ x, float* __restrict__ lse,
                                                      int64_t* __restrict__ argmax, int64_t rows, int64_t V) {
-  __shared__ float red[LB / 64];
+  __shared__ float red[ROW_LSE_RED];
   __shared__ int redi[LB / 64];
   const int64_t r = blockIdx.x;
   const T* xr = x + r * V;
-  float mx = -INFINITY;
-  int mi = 0x7fffffff;
-  for (int64_t v = threadIdx.x; v < V; v += LB) {
-    const float f = io<T>::ld(xr + v);
-    if (f > mx) { mx = f; mi = (int)v; }
+  float l;
+  int best;
+  row_stats_block([xr](int64_t v) { return io<T>::ld(xr + v); }, V, red, redi, argmax != nullptr, l, best);  // (row_lse.hpp: the order of the sum)
+  if (threadIdx.x == 0) {
+    if (argmax) argmax[r] = best;
+    lse[r] = l;
   }
-  const float bmx = block_max(mx, red);
-  float s = 0.f;
-  for (int64_t v = threadIdx.x; v < V; v += LB) s += __expf(io<T>::ld(xr + v) - bmx);
-  s = block_sum(s, red);
-  if (argmax) {
-    int cand = (mx == bmx) ? mi : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = cand;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int best = redi[0];
-      for (int i = 1; i < LB / 64; ++i) best = min(best, redi[i]);
-      argmax[r] = best;
-    }
-  }
-  if (threadIdx.x == 0) lse[r] = bmx + __logf(s);
 }
 
 // bf16 rows of V % 8 == 0 (16-byte aligned): one 16-byte load per 8 logits, the row stays in registers between the

@@ -164,28 +164,34 @@ def _to(thing, dev):
     return thing
 
 
-def _first_pass(model, batch, who, beam_size, N, candidates, opt: NBestOptions, want_encoder=False):
-    """Encode once, project, pick the candidates of every frame and search for the N best prefixes (blank = BOS): the plain kernel,
-    the LM-fused one when opt.fused, the biased one whenever opt.biased (the LM in it only when fused), the lm and the graph moved
-    to the device if need be.  The list's score is the search's own: ctc itself unless fused or biased.  Returns (list, [encoder
-    output, its mask] with want_encoder)."""
-    from joeys2t_amd.alignment import _ctc_frames
-    ctc_out, _, in_len, *enc = _ctc_frames(model, batch, who=who, want_lse=False, want_encoder=want_encoder)
-    B, T, V = ctc_out.shape
-    logits = ctc_out.float().contiguous()  # js2t_beam_pick reads f32
-    cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(B * T, V), min(int(candidates), V - 1), model.bos_index)
+def _search(model, logits, in_len, pack, beam_size, N, candidates, opt: NBestOptions):
+    """The n-best search over CTC logits that are there already - [B, T, V], or with `pack` (ops.PackedRows) packed rows [pack.rows, V];
+    in_len i64 [B] - for both callers, the utterance decoders through `_first_pass` and long_form.transcribe_long over its segments:
+    pick the candidates of every frame and search for the N best prefixes (blank = BOS) with the plain kernel, the LM-fused one when
+    opt.fused, the biased one whenever opt.biased (the LM in it only when fused), the lm and the graph moved to the device if need
+    be.  The list's score is the search's own: ctc itself unless fused or biased."""
+    V = logits.shape[-1]
+    logits = logits.float().contiguous()  # js2t_beam_pick reads f32
+    cand_id, cand_lp, lse = ops.ctc_beam_candidates(logits.view(-1, V), min(int(candidates), V - 1), model.bos_index)
     search = (logits, lse, cand_id, cand_lp, in_len, beam_size, N, model.bos_index, model.pad_index)
     in_beam = (_to(opt.lm, logits.device), model.bos_index, model.eos_index, opt.lm_weight, opt.length_bonus) if opt.fused else \
         (None, model.bos_index, model.eos_index, 0.0, 0.0)  # lm_fusion="rescore": the LM stays behind the search
     ctx = None
     if opt.biased:
-        ids, n, score, ctc, _, ctx = ops.ctc_beam_search_ctx(*search, *in_beam, _to(opt.context, logits.device), opt.context_weight)
+        ids, n, score, ctc, _, ctx = ops.ctc_beam_search_ctx(*search, *in_beam, _to(opt.context, logits.device), opt.context_weight, pack=pack)
     elif opt.fused:
-        ids, n, score, ctc, _ = ops.ctc_beam_search_lm(*search, *in_beam)
+        ids, n, score, ctc, _ = ops.ctc_beam_search_lm(*search, *in_beam, pack=pack)
     else:
-        ids, n, ctc = ops.ctc_beam_search(*search)
+        ids, n, ctc = ops.ctc_beam_search(*search, pack=pack)
         score = ctc
-    return NBest(ids, n, ctc, score, ctx), enc
+    return NBest(ids, n, ctc, score, ctx)
+
+
+def _first_pass(model, batch, who, beam_size, N, candidates, opt: NBestOptions, want_encoder=False):
+    """Encode once, project, and search (`_search`).  Returns (list, [encoder output, its mask] with want_encoder)."""
+    from joeys2t_amd.alignment import _ctc_frames
+    ctc_out, _, in_len, *enc = _ctc_frames(model, batch, who=who, want_lse=False, want_encoder=want_encoder)
+    return _search(model, ctc_out, in_len, None, beam_size, N, candidates, opt), enc
 
 
 def _attention_stage(model, lst: NBest, encoder_output, src_mask, ctc_weight):
@@ -279,6 +285,35 @@ def _finish(lst: NBest, opt: NBestOptions, n_best, return_parts):
 
 
 # ---------------------------------------------------------------- the two decoders
+def nbest_slots(who, opt: NBestOptions, beam_size, n_best, n_rescore):
+    """(beam_size, n_best, the slots to search for) of the encoder-only decoder - `ctc_beam_search`, and long_form.transcribe_long
+    over its segments - with that decoder's refusals of n_best / n_rescore (its docstring states them)"""
+    if not 1 <= n_best <= beam_size:
+        raise ValueError(f"{who}: n_best {n_best} outside 1..beam_size ({beam_size})")
+    if opt.fused and not opt.wide:
+        if n_rescore is not None:
+            raise ValueError(f"{who}: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
+    elif opt.rerank or opt.wide:
+        n_rescore = int(beam_size if n_rescore is None else n_rescore)
+        if not n_best <= n_rescore <= beam_size:
+            raise ValueError(f"{who}: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
+    elif n_rescore is not None:
+        raise ValueError(f"{who}: n_rescore without an lm or a length_bonus")
+    beam_size, n_best = int(beam_size), int(n_best)
+    return beam_size, n_best, n_rescore if opt.wide or (opt.rerank and not opt.fused) else n_best
+
+
+def ctc_stages(model, lst: NBest, opt: NBestOptions, n_best, return_parts):
+    """the stages of the encoder-only decoder behind its search, and its return layout (inside the caller's no_grad)"""
+    if opt.rerank and not opt.fused:  # (a fused search has applied the LM already)
+        _ngram_stage(model, lst, opt)
+    if return_parts:
+        _map_rank_stage(lst)
+    if opt.mbr:
+        _mbr_stage(lst, opt, min(lst.Lp, ops.edit_max_len() + 1))  # nobody has read the lengths: one above the limit is dead, not refused
+    return _finish(lst, opt, n_best, return_parts)
+
+
 def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, lm=None, lm_weight: float = 0.0,
                     length_bonus: float = 0.0, n_rescore: int = None, lm_fusion: str = "rescore", decision: str = "map",
                     mbr_scale: float = 1.0, return_parts: bool = False, confidence: bool = False, confidence_scale: float = 1.0,
@@ -303,28 +338,10 @@ def ctc_beam_search(model, batch, beam_size: int = 10, n_best: int = 1, candidat
     opt = NBestOptions("ctc_beam_search", lm, lm_weight, length_bonus, lm_fusion, decision, mbr_scale, confidence, confidence_scale, context,
                         context_weight)
     return_parts = return_parts or opt.confidence
-    if not 1 <= n_best <= beam_size:
-        raise ValueError(f"ctc_beam_search: n_best {n_best} outside 1..beam_size ({beam_size})")
-    if opt.fused and not opt.wide:
-        if n_rescore is not None:
-            raise ValueError("ctc_beam_search: n_rescore with lm_fusion='search' (the LM is in the beam: there is no list to re-rank)")
-    elif opt.rerank or opt.wide:
-        n_rescore = int(beam_size if n_rescore is None else n_rescore)
-        if not n_best <= n_rescore <= beam_size:
-            raise ValueError(f"ctc_beam_search: n_best {n_best} <= n_rescore {n_rescore} <= beam_size {beam_size} expected")
-    elif n_rescore is not None:
-        raise ValueError("ctc_beam_search: n_rescore without an lm or a length_bonus")
-    beam_size, n_best = int(beam_size), int(n_best)
-    N = n_rescore if opt.wide or (opt.rerank and not opt.fused) else n_best  # the slots searched for
+    beam_size, n_best, N = nbest_slots("ctc_beam_search", opt, beam_size, n_best, n_rescore)
     with torch.no_grad():
         lst, _ = _first_pass(model, batch, "ctc_beam_search", beam_size, N, candidates, opt)
-        if opt.rerank and not opt.fused:  # (a fused search has applied the LM already)
-            _ngram_stage(model, lst, opt)
-        if return_parts:
-            _map_rank_stage(lst)
-        if opt.mbr:
-            _mbr_stage(lst, opt, min(lst.Lp, ops.edit_max_len() + 1))  # nobody has read the lengths: one above the limit is dead, not refused
-        return _finish(lst, opt, n_best, return_parts)
+        return ctc_stages(model, lst, opt, n_best, return_parts)
 
 
 def ctc_attention_rescore(model, batch, beam_size: int = 10, n_best: int = 1, candidates: int = 8, ctc_weight: float = 0.3,

@@ -796,6 +796,62 @@ def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "Packed
     return path, tok_start, tok_end, frame_logp, score
 
 
+def ctc_stitch(logits3d, keep_lo, keep_hi, out_row, blank: int, rows: int = None, out=None):
+    """The kept frames of W encoder windows as one packed stream (js2t_ctc_stitch): logits3d [W, S, V] f32 / bf16; keep_lo / keep_hi /
+    out_row i32 [W] on the device - window w's frames keep_lo[w] .. keep_hi[w] - 1 become rows out_row[w] .. of the outputs.  Returns
+    (logits f32 [rows, V], lse f32 [rows], argmax i64 [rows], blank_lp f32 [rows]); rows no window writes are left as allocated.
+    out: those four, to write into (a second batch of windows of the same recording); rows is then theirs."""
+    _dev(logits3d, keep_lo, keep_hi, out_row)
+    if logits3d.dim() != 3 or not logits3d.is_contiguous():
+        raise Js2tError(f"ctc_stitch: contiguous [W, S, V] logits expected, got {tuple(logits3d.shape)}")
+    W, S, V = logits3d.shape
+    for name, t in (("keep_lo", keep_lo), ("keep_hi", keep_hi), ("out_row", out_row)):
+        if t.dtype != torch.int32 or t.shape != (W,) or not t.is_contiguous():
+            raise Js2tError(f"ctc_stitch: {name} must be a contiguous int32 [{W}] tensor, got {t.dtype} {tuple(t.shape)}")
+    dev = logits3d.device
+    if out is None:
+        if rows is None:
+            raise Js2tError("ctc_stitch: rows (of the stitched stream) or out expected")
+        out = (torch.empty((int(rows), V), dtype=torch.float32, device=dev), torch.empty((int(rows),), dtype=torch.float32, device=dev),
+               torch.empty((int(rows),), dtype=torch.int64, device=dev), torch.empty((int(rows),), dtype=torch.float32, device=dev))
+    st, lse, am, blp = out
+    _dev(*out)
+    rows = st.shape[0]
+    if st.shape != (rows, V) or any(t.shape != (rows,) for t in (lse, am, blp)) or (st.dtype, lse.dtype, am.dtype, blp.dtype) != \
+            (torch.float32, torch.float32, torch.int64, torch.float32) or not all(t.is_contiguous() for t in out):
+        raise Js2tError(f"ctc_stitch: out = contiguous (f32 [rows, {V}], f32 [rows], i64 [rows], f32 [rows]) expected")
+    check(lib().js2t_ctc_stitch(_p(logits3d), dt_code(logits3d), _p(keep_lo), _p(keep_hi), _p(out_row), _p(st), _p(lse), _p(am), _p(blp),
+                                W, S, V, rows, int(blank), _stream()), "js2t_ctc_stitch")
+    return st, lse, am, blp
+
+
+def ctc_segment(blank_lp, argmax, blank: int, log_threshold: float, min_silence: int, margin: int, max_len: int, max_segments: int,
+                workspace=None):
+    """A recording's posterior stream cut at its long blank runs (js2t_ctc_segment, which states the rule): blank_lp f32 [T] and argmax
+    i64 [T] as ctc_stitch returns them, the lengths in encoder frames.  Returns (n_seg i32 [1], seg_off i32 [max_segments + 1], seg_len
+    i64 [max_segments]) on the device; n_seg = -1 (and nothing else written) when there are more than max_segments segments.
+    workspace: a device buffer of >= js2t_ctc_segment_workspace_bytes(T) bytes to use instead of a fresh one."""
+    _dev(blank_lp, argmax, workspace)
+    T = blank_lp.numel()
+    if blank_lp.dtype != torch.float32 or argmax.dtype != torch.int64 or argmax.numel() != T or blank_lp.dim() != 1 or argmax.dim() != 1 \
+            or not blank_lp.is_contiguous() or not argmax.is_contiguous():
+        raise Js2tError(f"ctc_segment: contiguous blank_lp f32 [T] and argmax i64 [T] expected, got {blank_lp.dtype} {tuple(blank_lp.shape)} "
+                        f"and {argmax.dtype} {tuple(argmax.shape)}")
+    dev = blank_lp.device
+    need = lib().js2t_ctc_segment_workspace_bytes(T)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"ctc_segment: a contiguous workspace of {need} bytes expected")
+    ms = max(int(max_segments), 0)
+    n_seg = torch.empty((1,), dtype=torch.int32, device=dev)
+    seg_off = torch.empty((ms + 1,), dtype=torch.int32, device=dev)
+    seg_len = torch.empty((max(ms, 1),), dtype=torch.int64, device=dev)[:ms]
+    check(lib().js2t_ctc_segment(_p(blank_lp), _p(argmax), T, int(blank), float(log_threshold), int(min_silence), int(margin), int(max_len),
+                                 int(max_segments), _p(n_seg), _p(seg_off), _p(seg_len), _p(workspace), _stream()), "js2t_ctc_segment")
+    return n_seg, seg_off, seg_len
+
+
 def ctc_beam_workspace_bytes(B: int, T: int, beam: int) -> int:
     return lib().js2t_ctc_beam_workspace_bytes(B, T, beam)
 
