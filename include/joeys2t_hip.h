@@ -181,7 +181,9 @@ void js2t_gemm_panel_mode(int mode);
  * backward) and loss interpolation scaling (loss.py:164). */
 int js2t_axpby(const void* x, float a, const void* y, float b, void* out, int64_t n, int dt, js2t_stream stream);
 
-/* dst[i] = (dst_dt) src[i].  Autocast-style parameter/activation casts (training.py:558 autocast). */
+/* dst[i] = (dst_dt) src[i].  Autocast-style parameter/activation casts (training.py:558 autocast).
+ * Any element-aligned src / dst: four elements per thread only when src and dst are each aligned to four of their own elements
+ * (16 bytes f32, 8 bytes bf16), otherwise one element per thread over all n - same bits either way. */
 int js2t_cast(const void* src, int src_dt, void* dst, int dst_dt, int64_t n, js2t_stream stream);
 
 /* Weights of the LayerNorm fold (js2t_gemm ln_partial), re-derived from the fp32 masters after every optimizer update: for each
@@ -227,7 +229,9 @@ int js2t_transpose_groups(const void* src, void* dst, const int64_t* table, int3
 /* y[b,t,:] = dropout(x[b,t,:] + pe[t,:] (+ extra[b,t,:])) — PositionalEncoding.forward
  * (transformer_layers.py:204-213) + emb_dropout (encoders.py:273-276, decoders.py:599-602).
  * pe is f32[>=T, D] or NULL (plain dropout: ConformerEncoder's emb_dropout after its input Linear, encoders.py:433-435);
- * extra (prompt-mask embedding) may be NULL. */
+ * extra (prompt-mask embedding) may be NULL.
+ * D % 4 == 0, and x, extra, y (8 bytes bf16 / 16 bytes f32) and pe (16 bytes) aligned to four elements: JS2T_ERR_INVALID otherwise,
+ * nothing is launched. */
 int js2t_add_pe_dropout(const void* x, const float* pe, const void* extra, void* y, int64_t B, int64_t T,
                         int64_t D, int dt, float p, const uint64_t* rng_state, uint32_t rng_stream,
                         js2t_stream stream);
@@ -237,7 +241,8 @@ int js2t_dropout_bwd(const void* dy, void* dx, int64_t rows, int64_t cols, int d
                      const uint64_t* rng_state, uint32_t rng_stream, js2t_stream stream);
 
 /* dz = scale * dh * act'(z) — backward of the activations of builders.py:24-41 (relu, gelu, swish, tanh).
- * For ReLU, z may be the saved (post-dropout) output: its sign carries both the ReLU and the keep mask. */
+ * For ReLU, z may be the saved (post-dropout) output: its sign carries both the ReLU and the keep mask.
+ * At the kinks the gradients are torch's: relu'(0) = 0, hardswish'(-3) = 0, hardswish'(3) = 1. */
 int js2t_act_bwd(const void* dh, const void* z, void* dz, int64_t n, int act, int dt, float scale,
                  js2t_stream stream);
 

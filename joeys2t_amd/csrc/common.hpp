@@ -261,7 +261,8 @@ __device__ __forceinline__ float act_grad(float z, int act) {  // d act(z) / dz
       const float t = tanhf(z);
       return 1.f - t * t;
     }
-    case JS2T_ACT_HARDSWISH: return z < -3.f ? 0.f : (z > 3.f ? 1.f : (2.f * z + 3.f) * (1.f / 6.f));
+    // at the kinks the outer branches hold, as in torch's hardswish_backward: grad(-3) = 0, grad(3) = 1
+    case JS2T_ACT_HARDSWISH: return z <= -3.f ? 0.f : (z >= 3.f ? 1.f : (2.f * z + 3.f) * (1.f / 6.f));
     default: return 1.f;
   }
 }

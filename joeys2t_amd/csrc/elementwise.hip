@@ -14,7 +14,9 @@ inline int ew_grid(int64_t work_items) {
   return (int)g;
 }
 
-// ---- vector-of-4 accessors (4 consecutive elements; caller guarantees 4-element alignment) ----------
+inline size_t dt_bytes(int dt) { return dt == JS2T_BF16 ? 2 : 4; }
+
+// ---- vector-of-4 accessors (4 consecutive elements aligned to 4 elements: the host entry points check the pointers) ----------
 template <typename T> struct vec4;
 template <> struct vec4<float> {
   static __device__ __forceinline__ void ld(const float* p, float (&v)[4]) {
@@ -40,8 +42,8 @@ template <> struct vec4<uint16_t> {
 
 // ---------------------------------------------------------------- cast
 template <typename S, typename D>
-__global__ void cast_kernel(const S* __restrict__ src, D* __restrict__ dst, int64_t n) {
-  const int64_t n4 = n >> 2;
+__global__ void cast_kernel(const S* __restrict__ src, D* __restrict__ dst, int64_t n, int64_t n4) {
+  // n4 groups of four through the vector accessors (0 when a pointer is not aligned to four elements), the scalar loop the rest
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float v[4];
     vec4<S>::ld(src + 4 * i, v);
@@ -431,9 +433,12 @@ extern "C" int js2t_cast(const void* src, int src_dt, void* dst, int dst_dt, int
   if (n == 0) return JS2T_OK;
   JS2T_CHECK(src && dst && n > 0, "cast: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  const int g = ew_grid(n / 4 + 1);
+  // the four-wide loop needs src and dst aligned to four of their own elements (a view may start anywhere): else all scalar
+  const bool vec = ((uintptr_t)src % (4 * dt_bytes(src_dt))) == 0 && ((uintptr_t)dst % (4 * dt_bytes(dst_dt))) == 0;
+  const int64_t n4 = vec ? n >> 2 : 0;
+  const int g = ew_grid(vec ? n / 4 + 1 : n);
   DISPATCH_DT(src_dt, S, DISPATCH_DT(dst_dt, D, hipLaunchKernelGGL((cast_kernel<S, D>), dim3(g), dim3(EW_THREADS), 0, s,
-                                                                    (const S*)src, (D*)dst, n)));
+                                                                    (const S*)src, (D*)dst, n, n4)));
   JS2T_LAUNCH_CHECK();
   return JS2T_OK;
 }
@@ -479,6 +484,10 @@ extern "C" int js2t_add_pe_dropout(const void* x, const float* pe, const void* e
   JS2T_CHECK(x && y, "add_pe_dropout: null pointer");
   JS2T_CHECK(D % 4 == 0, "add_pe_dropout: D must be a multiple of 4 (got %lld)", (long long)D);
   JS2T_CHECK(p >= 0.f && p < 1.f && (p == 0.f || rng_state), "add_pe_dropout: bad dropout arguments");
+  JS2T_CHECK(dt == JS2T_F32 || dt == JS2T_BF16, "add_pe_dropout: bad dtype %d", dt);
+  const uintptr_t el4 = 4 * dt_bytes(dt);
+  JS2T_CHECK((uintptr_t)x % el4 == 0 && (uintptr_t)y % el4 == 0 && (!extra || (uintptr_t)extra % el4 == 0) && (!pe || (uintptr_t)pe % 16 == 0),
+             "add_pe_dropout: x, extra, y and pe must be aligned to four elements");
   DISPATCH_DT(dt, T, hipLaunchKernelGGL((add_pe_dropout_kernel<T>), dim3(ew_grid(B * T_ * D / 4)), dim3(EW_THREADS), 0,
                                         (hipStream_t)stream, (const T*)x, pe, (const T*)extra, (T*)y, B, T_, D, p,
                                         rng_state, rng_stream));
