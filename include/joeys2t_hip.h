@@ -450,6 +450,38 @@ int js2t_ctc_align(const void* logits, int dt, const float* lse, const int64_t* 
                    float* score, void* workspace, int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t blank,
                    const int32_t* row_offsets, js2t_stream stream);
 
+/* EXTENSION: CTC forced alignment of ONE whole recording to its transcript - js2t_ctc_align without the limit on 2*L+1 that one
+ * block's LDS sets, and with optional free ends.  logits [T, V] f32 or bf16 and lse f32 [T] (js2t_ctc_stitch's, js2t_row_lse's),
+ * targets i64 [L]; all device pointers.  Recursion, emission rule (an id outside 0..V-1: -inf), f32 arithmetic with one rounding
+ * per step and the tie rule are js2t_ctc_align's, word for word: with both flags 0 the five outputs are its outputs for B = 1,
+ * bit for bit, wherever both can run.
+ * Free ends (a recording carries music, an announcer, credits that the text lacks): with free_start the emission of state 0 is
+ * exactly 0.0f in every frame instead of lp_t(blank); with free_end the same holds for state S-1 (S = 2*L+1; for L = 0 there is
+ * one state and either flag frees it).  Two consequences, part of the contract: (1) a free frame costs nothing, so the free state
+ * also takes the blank frames next to the text and all but at least one frame of the first / last label's run - those two labels'
+ * spans come out shortened, never moved outside their run; (2) frame_logp of a free frame is 0.0f, the value that was counted.
+ * Outputs as js2t_ctc_align's for B = 1: path i32 [T], tok_start / tok_end i32 [L], frame_logp f32 [T], score f32 [1]; score
+ * equals the f32 sum of frame_logp in ascending t, bit for bit.  No path (T = 0, T below the labels plus the blanks that repeats
+ * need, or every path -inf): score -inf, path / tok_start / tok_end -1, frame_logp 0.
+ * Limits, each refused with a message and no launch: 0 <= L <= 1048575, 0 <= T < 2^31, 1 <= V, dt f32 or bf16; NULL pointers;
+ * a NULL workspace when js2t_ctc_align_long_workspace_bytes(T, L) is nonzero (it is 0 only for T = 0); a workspace that is not
+ * 16-byte aligned.  Workspace: with C = ceil((2*L+1) / 1024) block columns,
+ *   bytes = ceil(T / 16) * C * 4096   (back-pointers: 2 bits per (t, s), s padded to C * 1024)
+ *         + C * 4096                  (the carried state row of every column)
+ *         + C * 8192                  (the edge columns between neighbouring columns: two f32 per frame of a time tile, twice)
+ * - ten minutes (T = 15000, L = 3000): 23 126 016 bytes; an hour (T = 90000, L = 18000): 829 882 368 bytes.  Its contents on entry
+ * do not matter.
+ * js2t_ctc_align_long_tiles (host only) writes four values: {states per lane, states per wave, states per block column, frames
+ * per launch tile} - the sizes at which the kernels take another path.
+ * The call: one plain launch per anti-diagonal of (time tile, block column), one back-trace launch, one output launch, all on
+ * `stream`; no block waits for another block, no allocation, no host synchronisation, no atomics - the launch sequence depends on
+ * (T, L) alone, so the call can be captured and replayed, and gives the same bits every time. */
+int64_t js2t_ctc_align_long_workspace_bytes(int64_t T, int64_t L);
+void js2t_ctc_align_long_tiles(int32_t* out);
+int js2t_ctc_align_long(const void* logits, int dt, const float* lse, const int64_t* targets, int32_t* path, int32_t* tok_start,
+                        int32_t* tok_end, float* frame_logp, float* score, void* workspace, int64_t T, int64_t V, int64_t L,
+                        int64_t blank, int free_start, int free_end, js2t_stream stream);
+
 /* EXTENSION (the reference has no encoder-only n-best decoder): CTC prefix beam search - the beam search over the CTC output alone
  * that sums the probability of ALL alignments of a labelling (js2t_ctc_collapse reads the best path only).  One launch, one block
  * per utterance; natural logarithms, f32.  logits / lse / in_len / blank / row_offsets and the clamp T_b = clamp(in_len[b], 0, T) as

@@ -121,6 +121,69 @@ def align_hypotheses(model, batch, ids, pad_index: Optional[int] = None, frame_s
                         frame_shift_ms=frame_shift_ms)
 
 
+def _token_ids(tokens, who: str) -> np.ndarray:
+    """a 1-d integer sequence (list, array or tensor) as i64 on the host; anything else is a ValueError"""
+    if torch.is_tensor(tokens):
+        tokens = tokens.detach().cpu().numpy()
+    ids = np.asarray(tokens)
+    if ids.ndim == 1 and ids.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if ids.ndim != 1 or ids.dtype.kind not in "iu":
+        raise ValueError(f"{who}: tokens must be a 1-d integer sequence, got shape {ids.shape} of {ids.dtype}")
+    return np.ascontiguousarray(ids, dtype=np.int64)
+
+
+def align_stream(stream, tokens, blank: int, sec: float, free_start: bool = True, free_end: bool = True) -> Alignment:
+    """Align the token ids of a whole recording's transcript to its stitched posterior stream (`long_form.stitch_posteriors`' result:
+    logits f32 [T, V], lse, ...) with js2t_ctc_align_long; `sec`: seconds per encoder frame (`frame_seconds`).  free_start / free_end:
+    audio in front of / behind the text (music, an announcer) is taken by a state that costs nothing; the first / last token's
+    span is then shortened inside its run, and the frames the free state took count 0 in `score` (the header states both)."""
+    from joeys2t_amd import ops
+    ids = _token_ids(tokens, "align_stream")
+    if not isinstance(stream, (tuple, list)) or len(stream) < 2 or not all(torch.is_tensor(t) for t in stream[:2]):
+        raise ValueError("align_stream: stream = (logits [T, V], lse [T], ...) as stitch_posteriors returns it expected")
+    logits, lse = stream[0], stream[1]
+    if logits.dim() != 2 or lse.shape != (logits.shape[0],):
+        raise ValueError(f"align_stream: logits [T, V] and lse [T] expected, got {tuple(logits.shape)} and {tuple(lse.shape)}")
+    if not sec > 0.0:
+        raise ValueError(f"align_stream: {sec} seconds per frame")
+    with torch.no_grad():
+        trg = torch.from_numpy(ids).to(logits.device)
+        _, tok_start, tok_end, frame_logp, score = ops.ctc_align_long(logits.contiguous(), lse.contiguous(), trg, int(blank),
+                                                                      free_start=free_start, free_end=free_end)
+        return alignments(ids[None, :], [ids.size], tok_start[None, :], tok_end[None, :], frame_logp[None, :], score, float(sec))[0]
+
+
+def utterance_spans(alignment: Alignment, token_counts: Sequence[int], window: int = 10) -> List[Tuple[float, float, float, float]]:
+    """The transcript of an aligned recording is a run of sentences, sentence u has token_counts[u] tokens (their sum: the aligned
+    tokens; none is 0).  Returns per sentence (start, end, mean_logp, worst_logp): the seconds of its first token's start and its last
+    token's end; the mean of its tokens' `logp` over its FRAMES (weighted as `word_segments` weights a word); and the least such
+    mean over every run of `window` consecutive tokens of the sentence (the whole sentence if it is shorter) - low where the text
+    does not match the audio.  Pure host code."""
+    counts = [int(n) for n in token_counts]
+    window = int(window)
+    if window < 1:
+        raise ValueError(f"utterance_spans: window {window} below 1")
+    if any(n < 1 for n in counts):
+        raise ValueError("utterance_spans: a sentence of no tokens")
+    if sum(counts) != len(alignment.tokens):
+        raise ValueError(f"utterance_spans: {sum(counts)} tokens in the sentences, {len(alignment.tokens)} aligned")
+    frames = [e - s for s, e in zip(alignment.start_frame, alignment.end_frame)]
+    mass = [lp * n for lp, n in zip(alignment.logp, frames)]
+
+    def mean(i, j):
+        n = sum(frames[i:j])
+        return sum(mass[i:j]) / n if n else float("nan")
+
+    out, i = [], 0
+    for n in counts:
+        j = i + n
+        w = min(window, n)
+        out.append((alignment.start[i], alignment.end[j - 1], mean(i, j), min(mean(a, a + w) for a in range(i, j - w + 1))))
+        i = j
+    return out
+
+
 def word_segments(pieces: Sequence[str], alignment: Alignment) -> List[Tuple[str, float, float, float]]:
     """Merge the token spans of `alignment` into words: `pieces` are the sentence pieces of its tokens, a piece that begins with the
     word marker opens a new word (so does the first piece).  Returns (word, start, end, mean logp) per word - start / end in seconds,

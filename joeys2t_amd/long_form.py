@@ -243,3 +243,31 @@ def transcribe_long(model, audio, *, window: int, overlap: int, batch_size: int 
     return decode_stream(model, stream, min_silence=min_silence, silence_threshold=silence_threshold, margin=margin, max_segment=max_segment,
                          beam_size=beam_size, n_best=n_best, candidates=candidates, timestamps=timestamps, frame_shift_ms=frame_shift_ms,
                          **nbest_options)
+
+
+def align_long(model, audio, tokens, *, window: int, overlap: int, batch_size: int = 8, cmvn=None, sample_rate: int = 16000,
+               n_mel_bins: int = 80, free_start: bool = True, free_end: bool = True, frame_shift_ms: float = 10.0, utterances=None):
+    """A recording and its transcript to timestamps: `stitch_posteriors` (audio, window, overlap, batch_size, cmvn, sample_rate,
+    n_mel_bins), then `alignment.align_stream` - js2t_ctc_align_long over the whole stream, blank = model.bos_index.  tokens: the
+    transcript's token ids, a 1-d integer sequence of any length the kernel's header allows.  free_start / free_end (default on): the
+    recording may begin / end with audio the text lacks; the header of js2t_ctc_align_long states what that does to the first and
+    last token's span.  Returns the alignment.Alignment of the recording (seconds: `alignment.frame_seconds` per encoder frame;
+    `alignment.word_segments` works on it unchanged); with utterances = the token count of every sentence of the transcript, the
+    pair (Alignment, `alignment.utterance_spans` of it).  Raises ValueError for a model without a CTC layer and for tokens that
+    are not a 1-d integer sequence.  Not measured, not claimed: the accuracy of the timestamps on a trained model, and what the
+    window stitching does to them."""
+    from joeys2t_amd import alignment
+    who = "align_long"
+    if getattr(model.decoder, "ctc_output_layer", None) is None:
+        raise ValueError(f"{who}: the model has no CTC output layer (loss: crossentropy-ctc)")
+    ids = alignment._token_ids(tokens, who)
+    if utterances is not None and sum(int(n) for n in utterances) != ids.size:
+        raise ValueError(f"{who}: utterances sum to {sum(int(n) for n in utterances)} tokens, {ids.size} given")
+    plan_windows(1, window, overlap, _stride(model))
+    stream = stitch_posteriors(model, audio, window=window, overlap=overlap, batch_size=batch_size, cmvn=cmvn, sample_rate=sample_rate,
+                               n_mel_bins=n_mel_bins)
+    al = alignment.align_stream(stream, ids, int(model.bos_index), alignment.frame_seconds(model, frame_shift_ms), free_start=free_start,
+                                free_end=free_end)
+    if utterances is None:
+        return al
+    return al, alignment.utterance_spans(al, utterances)

@@ -796,6 +796,49 @@ def ctc_align(logits3d, lse, targets, in_len, tgt_len, blank: int, pack: "Packed
     return path, tok_start, tok_end, frame_logp, score
 
 
+def ctc_align_long_workspace_bytes(T: int, L: int) -> int:
+    return lib().js2t_ctc_align_long_workspace_bytes(T, L)
+
+
+def ctc_align_long_tiles():
+    """(states per lane, states per wave, states per block column, frames per launch tile) of js2t_ctc_align_long"""
+    out = (C.c_int32 * 4)()
+    lib().js2t_ctc_align_long_tiles(C.cast(out, C.c_void_p))
+    return tuple(out)
+
+
+def ctc_align_long(logits, lse, targets, blank: int, free_start: bool = False, free_end: bool = False, workspace=None):
+    """CTC forced alignment of ONE recording (js2t_ctc_align_long): logits [T, V] f32 / bf16 and lse f32 [T] (ctc_stitch's, row_lse's),
+    targets i64 [L], any L the header allows.  free_start / free_end: state 0 / the last state costs nothing (audio the text lacks).
+    Returns (path i32[T], tok_start, tok_end i32[L], frame_logp f32[T], score f32[1]) as ctc_align does for B = 1; score -inf,
+    path / spans -1 and frame_logp 0 when there is no path.
+    workspace: a device buffer of >= ctc_align_long_workspace_bytes(T, L) bytes to use instead of a fresh one (contents are ignored)."""
+    _dev(logits, lse, targets, workspace)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise Js2tError(f"ctc_align_long: contiguous [T, V] logits expected, got {tuple(logits.shape)}")
+    T, V = logits.shape
+    if lse.dtype != torch.float32 or lse.shape != (T,) or not lse.is_contiguous():
+        raise Js2tError(f"ctc_align_long: lse must be a contiguous float32 [{T}] tensor, got {lse.dtype} {tuple(lse.shape)}")
+    if targets.dtype != torch.int64 or targets.dim() != 1 or not targets.is_contiguous():
+        raise Js2tError(f"ctc_align_long: targets must be a contiguous int64 [L] tensor, got {targets.dtype} {tuple(targets.shape)}")
+    L = targets.shape[0]
+    dev = logits.device
+    need = ctc_align_long_workspace_bytes(T, L)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous():
+        raise Js2tError(f"ctc_align_long: a contiguous workspace of {need} bytes expected")
+    path = torch.empty((T,), dtype=torch.int32, device=dev)
+    tok_start = torch.empty((L,), dtype=torch.int32, device=dev)
+    tok_end = torch.empty((L,), dtype=torch.int32, device=dev)
+    frame_logp = torch.empty((T,), dtype=torch.float32, device=dev)
+    score = torch.empty((1,), dtype=torch.float32, device=dev)
+    check(lib().js2t_ctc_align_long(_p(logits), dt_code(logits), _p(lse), _p(targets), _p(path), _p(tok_start), _p(tok_end), _p(frame_logp),
+                                    _p(score), _p(workspace), T, V, L, int(blank), int(bool(free_start)), int(bool(free_end)), _stream()),
+          "js2t_ctc_align_long")
+    return path, tok_start, tok_end, frame_logp, score
+
+
 def ctc_stitch(logits3d, keep_lo, keep_hi, out_row, blank: int, rows: int = None, out=None):
     """The kept frames of W encoder windows as one packed stream (js2t_ctc_stitch): logits3d [W, S, V] f32 / bf16; keep_lo / keep_hi /
     out_row i32 [W] on the device - window w's frames keep_lo[w] .. keep_hi[w] - 1 become rows out_row[w] .. of the outputs.  Returns
