@@ -881,7 +881,9 @@ int js2t_fbank(const float* wave, const int64_t* sample_off, const int64_t* fram
  * 1/sqrt(max(E[x^2] - mean^2, 1e-10)) and fill[u] = mean of the normalised spectrogram, which is the value
  * SpecAugment writes into its masks (data_augmentation.py:45-46).  f32[U,F], f32[U,F], f32[U].
  * max_frames > 0: only the first max_frames frames of an utterance count - SpeechProcessor.__call__ truncates an
- * over-long evaluation utterance BEFORE CMVN (tokenizers.py:474-487). */
+ * over-long evaluation utterance BEFORE CMVN (tokenizers.py:474-487).
+ * 1 <= F <= 85: a block runs 12 frame groups of F threads, and 12 * F rounded up to a multiple of 64 has to stay within 1024
+ * threads (85 -> 1024, 86 -> 1088); both routes refuse anything else. */
 int js2t_cmvn_stats(const float* feat, const int64_t* frame_off, int32_t U, int32_t F, float* mean, float* istd,
                     float* fill, int32_t norm_means, int32_t norm_vars, int64_t max_frames, js2t_stream stream);
 /* The same statistics by EIGHT blocks per utterance (a 32-utterance batch otherwise keeps 32 of 256 CUs busy: 39 us) through a

@@ -13,6 +13,23 @@ namespace {
 constexpr int FB_WAVES = 4;       // frames per 256-thread block
 constexpr int FB_MAX_FFT = 1024;  // complex points per frame held in LDS
 
+// ln E of a mel energy (E >= FLT_EPSILON, normal).  Not __logf and not logf: both take v_log_f32 of E itself, which is good to one ulp
+// of log2 E, and for E in 2^32 .. 2^46 (speech at full scale) one ulp of log2 E is two ulps of ln E - the result is then off by up
+// to 1.9 ulp, the whole rounding allowance of tests/frontend_reference.py (2 ulp + 8 x 2^-24 x conditioning; 8.5 was needed).
+// Here v_log_f32 sees the mantissa only (|log2 m| <= 1/2: its ulp is 2^-25 at most), the exponent is added as e * ln 2 with ln 2 in
+// two parts (the high one has 9 trailing zero bits: e * LN2_HI is exact), in one fma: about half an ulp.  Six instructions more, twice
+// per lane and frame: nothing next to the transform.
+__device__ __forceinline__ float mel_log(float x) {
+  int e;
+  float m = frexpf(x, &e);  // [1/2, 1)
+  if (m < 0.70710678f) {
+    m *= 2.f;
+    e -= 1;
+  }
+  const float fe = (float)e;
+  return fmaf(fe, 0.693145751953125f, fmaf(__log2f(m), 0.69314718f, fe * 1.42860682e-6f));
+}
+
 // utterance of a global frame index: largest u with frame_off[u] <= f
 __device__ __forceinline__ int find_utt(const int64_t* __restrict__ frame_off, int U, int64_t f) {
   int lo = 0, hi = U;  // invariant frame_off[lo] <= f < frame_off[hi]
@@ -117,7 +134,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float* __restrict__ wa
       const float* wt = mel_w + mel_woff[m];
       float e = 0.f;
       for (int k = 0; k < ln; ++k) e += pw[st + k] * wt[k];
-      out[f * n_mel + m] = __logf(fmaxf(e, log_floor));
+      out[f * n_mel + m] = mel_log(fmaxf(e, log_floor));
     }
   }
 }
@@ -315,7 +332,7 @@ __global__ __launch_bounds__(256) void fbank512_kernel(const float* __restrict__
           e3 += pp[k + 3] * wt[k + 3];
         }
         for (; k < mln[q]; ++k) e0 += pp[k] * wt[k];
-        out[f * n_mel + mb] = __logf(fmaxf((e0 + e1) + (e2 + e3), log_floor));
+        out[f * n_mel + mb] = mel_log(fmaxf((e0 + e1) + (e2 + e3), log_floor));
       }
     }
     for (int mb = lane + 128; mb < n_mel; mb += 64) {  // more than 128 bins: the plain loop
@@ -323,7 +340,7 @@ __global__ __launch_bounds__(256) void fbank512_kernel(const float* __restrict__
       const float* wt = mel_w + mel_woff[mb];
       float e = 0.f;
       for (int k = 0; k < ln; ++k) e += pw[st + k] * wt[k];
-      out[f * n_mel + mb] = __logf(fmaxf(e, log_floor));
+      out[f * n_mel + mb] = mel_log(fmaxf(e, log_floor));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // pw / img are rewritten by the next frame
   }
@@ -333,6 +350,8 @@ __global__ __launch_bounds__(256) void fbank512_kernel(const float* __restrict__
 // mean[u,c] = mean_t x ; istd[u,c] = 1/sqrt(max(sum x^2 / T - mean^2, 1e-10)) ; fill[u] = mean of the normalised
 // spectrogram (SpecAugment's mask value).  Accumulated in f64.
 constexpr int CM_GROUPS = 12;  // frame groups per block: 12 x 80 bins = 960 threads share a piece of an utterance
+constexpr int CM_MAX_F = 85;   // most feature bins: 12 x 85 = 1020 threads round up to 1024, 12 x 86 to 1088
+static_assert(((CM_GROUPS * CM_MAX_F + 63) / 64) * 64 <= 1024 && ((CM_GROUPS * (CM_MAX_F + 1) + 63) / 64) * 64 > 1024, "CM_MAX_F");
 constexpr int CM_SPLIT = 8;    // pieces per utterance: 32 utterances alone would keep 32 of 256 CUs busy pulling 480 KB each (39 us)
 // phase 1: block (u, p) sums piece p of utterance u's kept frames -> part[u][p][2][F] (f64); phase 2 (cmvn_finish_kernel): one block
 // per utterance adds the pieces in order and writes mean / istd / fill.  Fixed orders: bit-reproducible.
@@ -542,9 +561,9 @@ extern "C" int js2t_cmvn_stats(const float* feat, const int64_t* frame_off, int3
                                float* fill, int32_t norm_means, int32_t norm_vars, int64_t max_frames, js2t_stream stream) {
   if (U == 0) return JS2T_OK;
   JS2T_CHECK(feat && frame_off && mean && istd && fill, "cmvn_stats: null pointer");
-  JS2T_CHECK(F > 0 && F <= 256, "cmvn_stats: 1..256 feature bins supported");
+  JS2T_CHECK(F > 0 && F <= CM_MAX_F, "cmvn_stats: 1..%d feature bins supported (%d frame groups x F threads, rounded up to 64, fit 1024)",
+             CM_MAX_F, CM_GROUPS);
   const int threads = ((CM_GROUPS * F + 63) / 64) * 64;
-  JS2T_CHECK(threads <= 1024, "cmvn_stats: too many feature bins");
   const size_t lds = sizeof(double) * (2 * CM_GROUPS * F + F);
   hipLaunchKernelGGL(cmvn_stats_kernel, dim3(U), dim3(threads), lds, (hipStream_t)stream, feat, frame_off, F, mean, istd, fill,
                      norm_means, norm_vars, max_frames);
@@ -559,9 +578,9 @@ extern "C" int js2t_cmvn_stats_ws(const float* feat, const int64_t* frame_off, i
                                   int32_t norm_means, int32_t norm_vars, int64_t max_frames, double* workspace, js2t_stream stream) {
   if (U == 0) return JS2T_OK;
   JS2T_CHECK(feat && frame_off && mean && istd && fill, "cmvn_stats: null pointer");
-  JS2T_CHECK(F > 0 && F <= 256, "cmvn_stats: 1..256 feature bins supported");
+  JS2T_CHECK(F > 0 && F <= CM_MAX_F, "cmvn_stats: 1..%d feature bins supported (%d frame groups x F threads, rounded up to 64, fit 1024)",
+             CM_MAX_F, CM_GROUPS);
   const int threads = ((CM_GROUPS * F + 63) / 64) * 64;
-  JS2T_CHECK(threads <= 1024, "cmvn_stats: too many feature bins");
   JS2T_CHECK(workspace, "cmvn_stats_ws: workspace required (js2t_cmvn_stats_workspace doubles)");
   hipLaunchKernelGGL(cmvn_partial_kernel, dim3(U, CM_SPLIT), dim3(threads), sizeof(double) * 2 * CM_GROUPS * F, (hipStream_t)stream, feat,
                      frame_off, F, workspace, max_frames);

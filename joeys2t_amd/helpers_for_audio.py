@@ -32,6 +32,46 @@ def _mel(f):
     return 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
 
 
+MIN_FFT, MAX_FFT = 64, 1024  # transform sizes js2t_fbank takes (fbank.hip: FB_MAX_FFT complex points of LDS per frame)
+
+
+def fbank_geometry(sample_rate: int, frame_length_ms: float = 25.0, frame_shift_ms: float = 10.0) -> Tuple[int, int, int]:
+    """(win_len, shift, n_fft) of the Kaldi framing at a sample rate: n_fft = the window length rounded up to a power of two."""
+    win_len = int(sample_rate * frame_length_ms * 0.001)
+    shift = int(sample_rate * frame_shift_ms * 0.001)
+    return win_len, shift, 1 << (max(win_len, 1) - 1).bit_length()
+
+
+def fbank_tables(sample_rate: int = 16000, n_mel_bins: int = 80, frame_length_ms: float = 25.0, frame_shift_ms: float = 10.0,
+                 low_freq: float = 20.0, high_freq: float = 0.0) -> Dict[str, np.ndarray]:
+    """The tables js2t_fbank reads, as host arrays (no device needed): window f32[win_len], tw_re / tw_im f32[n_fft / 2],
+    mel_start / mel_len / mel_woff int32[n_mel] and mel_w f32 (the filters' non-zero stretches, back to back in bin order)."""
+    n_mel = int(n_mel_bins)
+    win_len, _, n_fft = fbank_geometry(sample_rate, frame_length_ms, frame_shift_ms)
+    n = np.arange(win_len, dtype=np.float64)
+    window = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / (win_len - 1)))**0.85  # Povey
+    k = np.arange(n_fft // 2, dtype=np.float64)
+    ang = 2.0 * np.pi * k / n_fft
+    # triangular filters on the mel scale, evaluated at the FFT bin centres (Nyquist bin weight = 0)
+    nyq = 0.5 * sample_rate
+    hi = high_freq + nyq if high_freq <= 0.0 else high_freq
+    mlo, mhi = _mel(low_freq), _mel(hi)
+    delta = (mhi - mlo) / (n_mel + 1)
+    b = np.arange(n_mel, dtype=np.float64)[:, None]
+    left, center, right = mlo + b * delta, mlo + (b + 1) * delta, mlo + (b + 2) * delta
+    melf = _mel((sample_rate / n_fft) * np.arange(n_fft // 2, dtype=np.float64))[None, :]
+    banks = np.maximum(0.0, np.minimum((melf - left) / (center - left), (right - melf) / (right - center)))
+    starts, lens, woffs, wts = [], [], [], []
+    for m in range(n_mel):
+        nz = np.nonzero(banks[m] > 0)[0]
+        st, ln = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        starts.append(st), lens.append(ln), woffs.append(len(wts))
+        wts.extend(banks[m, st:st + ln].astype(np.float32).tolist())
+    return dict(window=window.astype(np.float32), tw_re=np.cos(ang).astype(np.float32), tw_im=(-np.sin(ang)).astype(np.float32),
+                mel_start=np.asarray(starts, dtype=np.int32), mel_len=np.asarray(lens, dtype=np.int32),
+                mel_woff=np.asarray(woffs, dtype=np.int32), mel_w=np.asarray(wts if wts else [0.0], dtype=np.float32))
+
+
 class FbankExtractor:
     """Device-resident tables (window, FFT twiddles, sparse mel filters) + launcher for js2t_fbank."""
 
@@ -41,37 +81,16 @@ class FbankExtractor:
         if self.device.type != "cuda":
             raise ops.Js2tError("FbankExtractor needs a cuda (ROCm) device: features are extracted by js2t_fbank")
         self.sample_rate, self.n_mel = int(sample_rate), int(n_mel_bins)
-        self.win_len = int(sample_rate * frame_length_ms * 0.001)
-        self.shift = int(sample_rate * frame_shift_ms * 0.001)
-        self.n_fft = 1 << (self.win_len - 1).bit_length()
+        self.win_len, self.shift, self.n_fft = fbank_geometry(sample_rate, frame_length_ms, frame_shift_ms)
+        if not (MIN_FFT <= self.n_fft <= MAX_FFT and self.shift > 0 and self.n_mel > 0):
+            raise ops.Js2tError(f"fbank: a {frame_length_ms} ms window at {sample_rate} Hz has {self.win_len} samples, a transform of "
+                                f"{self.n_fft} points; js2t_fbank takes {MIN_FFT}..{MAX_FFT} points (windows of {MIN_FFT // 2 + 1}.."
+                                f"{MAX_FFT} samples: {1000.0 * (MIN_FFT // 2 + 1) / frame_length_ms:.0f}.."
+                                f"{1000.0 * MAX_FFT / frame_length_ms:.0f} Hz at this window length)")
         self.preemph = float(preemph)
-        n = np.arange(self.win_len, dtype=np.float64)
-        window = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / (self.win_len - 1)))**0.85  # Povey
-        k = np.arange(self.n_fft // 2, dtype=np.float64)
-        ang = 2.0 * np.pi * k / self.n_fft
-        # triangular filters on the mel scale, evaluated at the FFT bin centres (Nyquist bin weight = 0)
-        nyq = 0.5 * sample_rate
-        hi = high_freq + nyq if high_freq <= 0.0 else high_freq
-        mlo, mhi = _mel(low_freq), _mel(hi)
-        delta = (mhi - mlo) / (self.n_mel + 1)
-        b = np.arange(self.n_mel, dtype=np.float64)[:, None]
-        left, center, right = mlo + b * delta, mlo + (b + 1) * delta, mlo + (b + 2) * delta
-        melf = _mel((sample_rate / self.n_fft) * np.arange(self.n_fft // 2, dtype=np.float64))[None, :]
-        banks = np.maximum(0.0, np.minimum((melf - left) / (center - left), (right - melf) / (right - center)))
-        starts, lens, woffs, wts = [], [], [], []
-        for m in range(self.n_mel):
-            nz = np.nonzero(banks[m] > 0)[0]
-            st, ln = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
-            starts.append(st), lens.append(ln), woffs.append(len(wts))
-            wts.extend(banks[m, st:st + ln].astype(np.float32).tolist())
-        dev = self.device
-        self.window = torch.tensor(window, dtype=torch.float32, device=dev)
-        self.tw_re = torch.tensor(np.cos(ang), dtype=torch.float32, device=dev)
-        self.tw_im = torch.tensor(-np.sin(ang), dtype=torch.float32, device=dev)
-        self.mel_start = torch.tensor(starts, dtype=torch.int32, device=dev)
-        self.mel_len = torch.tensor(lens, dtype=torch.int32, device=dev)
-        self.mel_woff = torch.tensor(woffs, dtype=torch.int32, device=dev)
-        self.mel_w = torch.tensor(wts if wts else [0.0], dtype=torch.float32, device=dev)
+        tables = fbank_tables(sample_rate, n_mel_bins, frame_length_ms, frame_shift_ms, low_freq, high_freq)
+        for name, arr in tables.items():
+            setattr(self, name, torch.from_numpy(arr).to(self.device))
         self._plans = {}
 
     def n_frames(self, n_samples: int) -> int:
