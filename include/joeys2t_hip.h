@@ -482,6 +482,48 @@ int js2t_ctc_align_long(const void* logits, int dt, const float* lse, const int6
                         int32_t* tok_end, float* frame_logp, float* score, void* workspace, int64_t T, int64_t V, int64_t L,
                         int64_t blank, int free_start, int free_end, js2t_stream stream);
 
+/* EXTENSION: phrase spotting in ONE recording's CTC stream - WHERE is a phrase said, and how well?  For each of K phrases a Viterbi
+ * recursion over CTC states with a FREE START IN EVERY FRAME, then a picker that turns the per-frame scores into disjoint hits.  One
+ * launch, one wavefront per phrase, one lane per state; no LDS, no workspace, no atomics.  All pointers are device pointers.
+ * Inputs.  logits [T, V] f32 or bf16 (converted to f32 exactly); norm f32 [T], a per-frame normaliser (the row maximum makes an
+ * emission the log of label probability / best label probability: <= 0, and exactly 0 where the label is the frame's arg-max);
+ * tokens i64 [K, Lmax], lengths i32 [K] with 1 <= lengths[k] <= Lmax <= 32 (tokens behind a phrase's length are never read);
+ * blank; log_threshold, a finite f32.
+ * States.  Phrase y_1 .. y_L has S = 2 L - 1 states: even j is label y_(j/2+1), odd j the blank between two labels.  No leading or
+ * trailing blank: a hit begins in a frame of y_1 and ends in a frame of y_L.
+ * Emission.  e_t(j) = logits[t, label_j] - norm[t], one f32 rounding; -inf for a label id, or a blank, outside 0 .. V-1.
+ * Recursion, one f32 rounding per step, v_-1(j) = -inf.  With every value v_t(j) travels b_t(j), the frame its path started in.
+ *   j = 0: the predecessor is v_t-1(0), keeping b_t-1(0), if v_t-1(0) >= 0; otherwise 0 with start t - the free start.  (With norm the
+ *          row maximum a restart never loses, so this is "on an exact tie keep the earlier start": a run of frames in which y_1 is the
+ *          arg-max belongs to the hit from its first frame.)
+ *   j >= 1: the predecessors are j, j-1 and j-2, the last only for even j with label_j != label_j-2 (js2t_ctc_align's skip
+ *          condition); tie rule as there: stay, then j-1, then j-2, a switch needs a strict >.  b comes from the chosen predecessor.
+ *   v_t(j) = best + e_t(j); b_t(j) = -1 where v_t(j) = -inf.
+ *   h_t = v_t(S-1), s_t = b_t(S-1): the best score over ALL starts and ALL alignments of the phrase that end in frame t.
+ * Picking, per phrase: one sweep in ascending t with the state (have, cs, cb, ce) and last_end = -1.  Frame t is a candidate when
+ * h_t >= log_threshold and s_t > last_end.  For a candidate, in this order:
+ *   no current hit:                             current = (h_t, s_t, t);
+ *   s_t > ce (disjoint from the current hit):   emit the current hit, last_end = ce, current = (h_t, s_t, t);
+ *   h_t > cs, or h_t == cs and s_t == cb:       current = (h_t, s_t, t)  - a better overlapping candidate replaces the current one,
+ *                                               an equal one with the same start extends the end over the last label's run;
+ *   otherwise the candidate is dropped.
+ * After the last frame the current hit, if any, is emitted.  Emitted hits are disjoint and ascending; hit = (start = cb, end = ce + 1,
+ * score = cs), the end one past the last frame.
+ * Outputs.  hit_count i32 [K]: the hits FOUND, which may exceed max_hits; hit_start / hit_end i32 and hit_score f32 [K, max_hits]:
+ * the first min(count, max_hits) entries of a row are written, the entries behind them are left untouched.  frame_score f32 [K, T]
+ * and frame_start i32 [K, T], each may be NULL: h_t and s_t (a detection curve).
+ * Refused with a message and no launch: T outside 0 .. 2^31 - 1, V < 1, K < 0 or K > 65535, Lmax < 1 or Lmax > 32, max_hits outside 1 .. 2^31 - 1, dt
+ * other than f32 / bf16, a log_threshold that is not finite, a NULL pointer (logits and norm may be NULL for T = 0, everything for
+ * K = 0, the two frame_* always).  K = 0 or T = 0: no launch, the K counts are zeroed.  lengths live on the device and are not
+ * checked: a length outside 1 .. Lmax is treated as the nearest of the two and the phrase's result is undefined (the Python layer
+ * refuses it); no read or write leaves the arrays.
+ * js2t_ctc_spot_tiles (host only) writes three values: {most labels per phrase, phrases per block, frames per prefetch group}.
+ * One plain launch on `stream`: capturable, and the same bits every time. */
+void js2t_ctc_spot_tiles(int32_t* out);
+int js2t_ctc_spot(const void* logits, int dt, const float* norm, const int64_t* tokens, const int32_t* lengths, int64_t K, int64_t Lmax,
+                  int32_t* hit_count, int32_t* hit_start, int32_t* hit_end, float* hit_score, int64_t max_hits, float* frame_score,
+                  int32_t* frame_start, int64_t T, int64_t V, int64_t blank, float log_threshold, js2t_stream stream);
+
 /* EXTENSION (the reference has no encoder-only n-best decoder): CTC prefix beam search - the beam search over the CTC output alone
  * that sums the probability of ALL alignments of a labelling (js2t_ctc_collapse reads the best path only).  One launch, one block
  * per utterance; natural logarithms, f32.  logits / lse / in_len / blank / row_offsets and the clamp T_b = clamp(in_len[b], 0, T) as

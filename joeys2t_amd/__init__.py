@@ -5,7 +5,7 @@ include/joeys2t_hip.h).  PyTorch provides device memory, streams, autograd routi
 """
 __version__ = "0.1.0"
 
-_LONG_FORM = ("plan_windows", "stitch_posteriors", "segment", "decode_stream", "transcribe_long", "align_long")  # joeys2t_amd.long_form: one recording to text
+_LONG_FORM = ("plan_windows", "stitch_posteriors", "segment", "decode_stream", "transcribe_long", "align_long", "spot_long")  # joeys2t_amd.long_form: one recording to text
 __all__ = ["long_form", *_LONG_FORM]
 
 

@@ -26,6 +26,20 @@ MAX_FAIL = 32       # JS2T_CONTEXT_MAX_FAIL
 MAX_V = 65535       # JS2T_CONTEXT_MAX_V
 
 
+def phrase_ids(phrases: Iterable, vocab):
+    """phrases: strings of whitespace-separated pieces, or sequences of pieces, in the vocabulary's own tokens.  Returns (the id
+    lists of the phrases kept, in order; the number dropped): a phrase with a piece the vocabulary does not hold is dropped."""
+    ids, dropped = [], 0
+    for p in phrases:
+        pieces = p.split() if isinstance(p, str) else list(p)
+        row = [vocab.lookup(tok) for tok in pieces]
+        if any(i == vocab.unk_index and tok != vocab.specials[0] for i, tok in zip(row, pieces)):
+            dropped += 1
+            continue
+        ids.append(row)
+    return ids, dropped
+
+
 class ContextGraph:
     """The automaton of a phrase set over V <= 65535 ids in the layout js2t_ctc_beam_search_ctx reads.  Build it with from_phrases
     or from_text; `.to(device)` puts the tables on the device (`nodes_dev` i32 [n_nodes, 4], `edges_dev` i64 [capacity, 2], the
@@ -114,14 +128,7 @@ class ContextGraph:
     def from_text(cls, phrases: Iterable, vocab, device=None, max_load: float = 0.5) -> "ContextGraph":
         """phrases: strings of whitespace-separated pieces, or sequences of pieces, in the vocabulary's own tokens (what
         NGramLM.from_arpa looks up).  A phrase with a piece the vocabulary does not hold is dropped; `.dropped` counts them."""
-        ids, dropped = [], 0
-        for p in phrases:
-            pieces = p.split() if isinstance(p, str) else list(p)
-            row = [vocab.lookup(tok) for tok in pieces]
-            if any(i == vocab.unk_index and tok != vocab.specials[0] for i, tok in zip(row, pieces)):
-                dropped += 1
-                continue
-            ids.append(row)
+        ids, dropped = phrase_ids(phrases, vocab)
         return cls.from_phrases(ids, len(vocab), device=device, max_load=max_load, dropped=dropped)
 
     # ------------------------------------------------------------ storage

@@ -271,3 +271,27 @@ def align_long(model, audio, tokens, *, window: int, overlap: int, batch_size: i
     if utterances is None:
         return al
     return al, alignment.utterance_spans(al, utterances)
+
+
+def spot_long(model, audio, phrases, *, window: int, overlap: int, batch_size: int = 8, cmvn=None, sample_rate: int = 16000,
+              n_mel_bins: int = 80, threshold: float = 0.5, max_hits: int = 64, frame_shift_ms: float = 10.0):
+    """Where in a recording are these phrases said: `stitch_posteriors` (audio, window, overlap, batch_size, cmvn, sample_rate,
+    n_mel_bins), then `spotting.find_phrases` - js2t_ctc_spot over the whole stream, blank = model.bos_index.  phrases: a list of 1-d
+    integer sequences of 1 .. 32 token ids (`spotting.phrases_from_text` makes them from pieces); threshold and max_hits:
+    find_phrases'.  Returns the list of spotting.PhraseHit sorted by (start_frame, phrase), frames and seconds
+    (`alignment.frame_seconds` per encoder frame) counted from the start of the recording.  Raises ValueError for a model without
+    a CTC layer and for what find_phrases refuses, before the model runs.  Not measured, not claimed: detection accuracy or false-alarm
+    rate on a trained model, and what the window stitching does to them."""
+    from joeys2t_amd import alignment, spotting
+    who = "spot_long"
+    if getattr(model.decoder, "ctc_output_layer", None) is None:
+        raise ValueError(f"{who}: the model has no CTC output layer (loss: crossentropy-ctc)")
+    spotting._phrase_ids(phrases, 32)  # (the refusals, before the model is touched)
+    spotting._log_threshold(threshold)
+    if int(max_hits) < 1:
+        raise ValueError(f"{who}: max_hits {max_hits} below 1")
+    plan_windows(1, window, overlap, _stride(model))
+    stream = stitch_posteriors(model, audio, window=window, overlap=overlap, batch_size=batch_size, cmvn=cmvn, sample_rate=sample_rate,
+                               n_mel_bins=n_mel_bins)
+    return spotting.find_phrases(stream, phrases, int(model.bos_index), alignment.frame_seconds(model, frame_shift_ms), threshold=threshold,
+                                 max_hits=max_hits)

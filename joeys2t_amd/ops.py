@@ -839,6 +839,53 @@ def ctc_align_long(logits, lse, targets, blank: int, free_start: bool = False, f
     return path, tok_start, tok_end, frame_logp, score
 
 
+def ctc_spot_tiles():
+    """(most labels per phrase, phrases per block, frames per prefetch group) of js2t_ctc_spot"""
+    out = (C.c_int32 * 3)()
+    lib().js2t_ctc_spot_tiles(C.cast(out, C.c_void_p))
+    return tuple(out)
+
+
+def ctc_spot(logits, norm, tokens, lengths, blank: int, log_threshold: float, max_hits: int = 64, frame_scores: bool = False, out=None):
+    """Phrase spotting in ONE recording's CTC stream (js2t_ctc_spot, whose header comment states the rule): logits [T, V] f32 / bf16,
+    norm f32 [T] (the per-frame normaliser, e.g. the row maximum), tokens i64 [K, Lmax] and lengths i32 [K] (1 <= lengths[k] <= Lmax
+    <= ctc_spot_tiles()[0]; the lengths are on the device and are not read here - no host synchronisation, the call can be captured -
+    so the caller vouches for them, as spotting.find_phrases does from its host lists), log_threshold finite.
+    Returns (hit_count i32 [K], hit_start, hit_end i32 [K, max_hits], hit_score f32 [K, max_hits], frame_score f32 [K, T] or None,
+    frame_start i32 [K, T] or None): hit_count is the number of hits found, which may exceed max_hits; only the first
+    min(count, max_hits) entries of a row are written.  out: those six (the last two None without frame_scores) to write into."""
+    _dev(logits, norm, tokens, lengths)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise Js2tError(f"ctc_spot: contiguous [T, V] logits expected, got {tuple(logits.shape)}")
+    T, V = logits.shape
+    if norm.dtype != torch.float32 or norm.shape != (T,) or not norm.is_contiguous():
+        raise Js2tError(f"ctc_spot: norm must be a contiguous float32 [{T}] tensor, got {norm.dtype} {tuple(norm.shape)}")
+    if tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.shape[1] < 1 or not tokens.is_contiguous():
+        raise Js2tError(f"ctc_spot: tokens must be a contiguous int64 [K, Lmax] tensor with Lmax >= 1, got {tokens.dtype} {tuple(tokens.shape)}")
+    K, Lmax = tokens.shape
+    if lengths.dtype != torch.int32 or lengths.shape != (K,) or not lengths.is_contiguous():
+        raise Js2tError(f"ctc_spot: lengths must be a contiguous int32 [{K}] tensor, got {lengths.dtype} {tuple(lengths.shape)}")
+    max_hits = int(max_hits)
+    dev = logits.device
+    if out is None:
+        rows = (K, max(max_hits, 0))
+        out = (torch.empty((K,), dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
+               torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.float32, device=dev),
+               torch.empty((K, T), dtype=torch.float32, device=dev) if frame_scores else None,
+               torch.empty((K, T), dtype=torch.int32, device=dev) if frame_scores else None)
+    count, start, end, score, fscore, fstart = out
+    _dev(*out)
+    want = ((count, (K,), torch.int32), (start, (K, max_hits), torch.int32), (end, (K, max_hits), torch.int32),
+            (score, (K, max_hits), torch.float32), (fscore, (K, T), torch.float32), (fstart, (K, T), torch.int32))
+    if any(t is None for t in out[:4]) or any(t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous())
+                                              for t, shape, dt in want):
+        raise Js2tError(f"ctc_spot: out = contiguous (i32 [{K}], i32 [{K}, {max_hits}] twice, f32 [{K}, {max_hits}], f32 [{K}, {T}] or None, "
+                        f"i32 [{K}, {T}] or None) expected")
+    check(lib().js2t_ctc_spot(_p(logits), dt_code(logits), _p(norm), _p(tokens), _p(lengths), K, Lmax, _p(count), _p(start), _p(end),
+                              _p(score), max_hits, _p(fscore), _p(fstart), T, V, int(blank), float(log_threshold), _stream()), "js2t_ctc_spot")
+    return count, start, end, score, fscore, fstart
+
+
 def ctc_stitch(logits3d, keep_lo, keep_hi, out_row, blank: int, rows: int = None, out=None):
     """The kept frames of W encoder windows as one packed stream (js2t_ctc_stitch): logits3d [W, S, V] f32 / bf16; keep_lo / keep_hi /
     out_row i32 [W] on the device - window w's frames keep_lo[w] .. keep_hi[w] - 1 become rows out_row[w] .. of the outputs.  Returns
