@@ -777,6 +777,59 @@ int js2t_ctc_segment(const float* blank_lp, const int64_t* argmax, int64_t T, in
                      int32_t margin, int32_t max_len, int32_t max_segments, int32_t* n_seg, int32_t* seg_off, int64_t* seg_len,
                      void* workspace, js2t_stream stream);
 
+/* EXTENSION (the reference decodes finished utterances): live CTC decoding - the prefix beam search of js2t_ctc_beam_search_ctx as a
+ * RESUMABLE step over B independent streams, with a causal endpoint rule beside it.  A call takes the next rows of every stream,
+ * continues each stream's search where the last call left it, closes the utterances that end inside the rows and writes them as
+ * final records.  One launch, one block of 256 threads per stream; no atomics, no allocation, no synchronisation: the same bits on
+ * every run and under graph replay.  The frame recursion, the EOS epilogue and the back-trace are the one-shot kernel's own code
+ * (joeys2t_amd/csrc/ctc_beam_core.hpp, instantiated by both).  Natural logarithms, f32.
+ * Rows: logits f32 [rows, V], lse f32 [rows], argmax i64 [rows] (js2t_ctc_stitch's or js2t_row_lse's), cand_id i64 / cand_lp f32
+ * [rows, n_cand] (js2t_beam_pick with the blank forbidden).  row_offsets i32 [B + 1] on the device: stream b gets the rows
+ * row_offsets[b] .. row_offsets[b + 1] - 1, possibly none; the offsets are clamped to 0 .. rows and to ascending order.  flush i32 [B]
+ * on the device, or NULL for "no stream".  The LM, the context graph, bos / eos and the three weights: js2t_ctc_beam_search_ctx's.
+ * The rule (part of the contract; tests/ctc_stream_reference.py restates it in NumPy).  lp_b(t) = logits[t, blank] - lse[t]:
+ *   - frame t is SILENT iff argmax[t] == blank and lp_b(t) >= log_threshold (js2t_ctc_segment's test; a NaN: not silent);
+ *   - a stream is IDLE or in SPEECH, and counts its frames from 0 for as long as its state lives.  IDLE: a silent frame is consumed
+ *     and not searched; the first frame t that is not silent opens a segment - start = t, n = 0, run = 0, the beam is the empty
+ *     prefix - and is handled as a SPEECH frame;
+ *   - SPEECH: the frame goes through the recursion; n += 1; run = run + 1 if the frame is silent, else 0;
+ *   - the segment [start, start + n) is FINAL, and the stream IDLE again, when run == min_silence (why = 1, an endpoint: the trailing
+ *     silence belongs to the segment; min_silence = 0: never) or else when n == max_len (why = 2, forced);
+ *   - after the call's last row, flush[b] != 0 makes an open segment final (why = 3).  A flush in IDLE does nothing.
+ * A final record is what js2t_ctc_beam_search_ctx returns for the rows [start, start + n) alone, bit for bit - labels, lengths, score /
+ * ctc / lm / ctx with the EOS term and the final re-ranking - in slot (b, i), i = 0 .. in the order the segments end: fin_ids i64
+ * [B, max_finals, n_best, max_len] pad-filled, fin_len i32 / fin_score / fin_ctc / fin_lm f32 / fin_ctx i32 [B, max_finals, n_best],
+ * fin_start i64 / fin_n i32 / fin_why i32 [B, max_finals].  n_final i32 [B] = the records written by this call; the other slots keep
+ * their contents.  When a stream's max_finals slots are full it consumes no further row in this call: consumed i32 [B] = the rows
+ * it took, and the caller sends the rest again (a flush is honoured only by a call that consumes all its rows).  Nothing is lost or
+ * decoded twice.
+ * The partial result, per stream and call: part_ids i64 [B, max_len] = the labels of beam slot 0 in the order of the FRAME key, i.e.
+ * before any EOS term and before the final re-ranking (only part_len[b] entries are written); part_len i32 [B]; stable_len i32 [B] =
+ * the longest common prefix of ALL live beam slots - every later hypothesis of the segment descends from one of them, so these
+ * labels of part_ids can no longer change before the segment ends; part_start i64 [B] = the open segment's start, -1 when IDLE
+ * (part_len = stable_len = 0 then).
+ * state: js2t_ctc_stream_state_bytes(B, beam, max_len) bytes, 16-byte aligned, one fixed stride per stream (the total / B).  A stream
+ * whose state is all zero bytes is fresh: a reset is a memset.  It holds the phase, the frame count (i64), start (i64), n, run, the
+ * number of live beam slots, the beam itself (2 KB; slots that are not live are stored as zeros) and the trie, 1 + beam * max_len
+ * (parent, token) nodes indexed by the frame's position IN THE SEGMENT.  beam and max_len belong to the state: they must not change
+ * between calls.  Written with ordinary vector stores.
+ * Main property: however a stream's rows are cut into calls (empty calls included), the final records, their order and the state
+ * after the last row are the same bits.
+ * Limits: those of js2t_ctc_beam_search_ctx with beam * max_len < 2^31 in place of beam * T; 1 <= max_finals; 1 <= max_len; 0 <=
+ * min_silence; log_threshold not NaN; 0 <= rows < 2^31 (rows = 0: the row arrays may be NULL).  Every limit and every NULL is refused
+ * before anything is launched; B = 0 returns 0. */
+int64_t js2t_ctc_stream_state_bytes(int64_t B, int32_t beam, int64_t max_len);
+int js2t_ctc_stream_step(const float* logits, const float* lse, const int64_t* argmax, const int64_t* cand_id, const float* cand_lp,
+                         const int32_t* row_offsets, const int32_t* flush, const float* uni, const void* table, int64_t capacity,
+                         int32_t max_probe, int32_t lm_order, const void* ctx_nodes, const void* ctx_edges, int64_t ctx_capacity,
+                         int32_t ctx_max_probe, int32_t ctx_n_nodes, int32_t ctx_max_fail, void* state, int64_t* fin_ids,
+                         int32_t* fin_len, float* fin_score, float* fin_ctc, float* fin_lm, int32_t* fin_ctx, int64_t* fin_start,
+                         int32_t* fin_n, int32_t* fin_why, int32_t* consumed, int32_t* n_final, int64_t* part_ids, int32_t* part_len,
+                         int32_t* stable_len, int64_t* part_start, int64_t B, int64_t rows, int64_t V, int32_t beam, int32_t n_cand,
+                         int32_t n_best, int32_t max_finals, int64_t max_len, int64_t blank, int64_t pad, int64_t bos, int64_t eos,
+                         float lm_weight, float context_weight, float length_bonus, float log_threshold, int32_t min_silence,
+                         js2t_stream stream);
+
 /* EXTENSION (the reference has no edit distance on the device): unit-cost Levenshtein distances of pairs of rows of i64 ids, one wave
  * per pair.  Row r of `a` lies at a + r * a_stride and has a_len[r] (i32) ids; it is compared with row r / group of `b`, at
  * b + (r / group) * b_stride with b_len[r / group] ids: group = 1 pairs the rows one to one, group = N compares the N hypotheses of an

@@ -6,12 +6,14 @@ include/joeys2t_hip.h).  PyTorch provides device memory, streams, autograd routi
 __version__ = "0.1.0"
 
 _LONG_FORM = ("plan_windows", "stitch_posteriors", "segment", "decode_stream", "transcribe_long", "align_long", "spot_long")  # joeys2t_amd.long_form: one recording to text
-__all__ = ["long_form", *_LONG_FORM]
+_STREAMING = ("CTCStreamDecoder", "StreamingTranscriber")  # joeys2t_amd.streaming: captions while the audio arrives
+__all__ = ["long_form", *_LONG_FORM, "streaming", *_STREAMING]
 
 
 def __getattr__(name):  # on first use: importing the package stays free of torch and of the library
-    if name == "long_form" or name in _LONG_FORM:
-        import importlib
-        module = importlib.import_module("joeys2t_amd.long_form")
-        return module if name == "long_form" else getattr(module, name)
+    for module_name, names in (("long_form", _LONG_FORM), ("streaming", _STREAMING)):
+        if name == module_name or name in names:
+            import importlib
+            module = importlib.import_module(f"joeys2t_amd.{module_name}")
+            return module if name == module_name else getattr(module, name)
     raise AttributeError(f"module 'joeys2t_amd' has no attribute '{name}'")

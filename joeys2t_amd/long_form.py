@@ -90,9 +90,6 @@ def stitch_posteriors(model, audio, *, window: int, overlap: int, batch_size: in
     features [n_frames, F] themselves.  cmvn: the data_augmentation.CMVN of the model's data config (SpeechProcessor.cmvn) or None;
     the statistics are taken per window (`finalize_features`).  Returns (logits f32 [T, V], lse f32 [T], argmax i64 [T], blank_lp
     f32 [T]) on the device, T = ceil(n_frames / stride); blank = model.bos_index."""
-    from joeys2t_amd.alignment import _ctc_frames
-    from joeys2t_amd.batch import Batch
-    from joeys2t_amd.data_augmentation import finalize_features
     if int(batch_size) < 1:
         raise ValueError(f"{WHO}: batch_size {batch_size} below 1")
     s = _stride(model)
@@ -110,18 +107,29 @@ def stitch_posteriors(model, audio, *, window: int, overlap: int, batch_size: in
         out = None
         for a in range(0, len(plan.start), int(batch_size)):
             b = min(a + int(batch_size), len(plan.start))
-            frames = plan.length[a:b]
-            chunk = torch.cat([feat[st:st + n] for st, n in zip(plan.start[a:b], frames)])  # (overlapping windows: ragged, back to back)
-            off = torch.tensor(np.concatenate([[0], np.cumsum(frames)]), dtype=torch.int64, device=dev)
-            src, _ = finalize_features(chunk, off, frames, cmvn=cmvn, specaugment=None)
-            batch = Batch(src=src, src_length=torch.tensor(frames, dtype=torch.int64), src_prompt_mask=None, trg=None, trg_length=None,
-                          trg_prompt_mask=None, indices=torch.arange(b - a), device=dev, pad_index=model.pad_index,
-                          eos_index=model.eos_index, is_train=False, task="S2T", n_gpu=1)
-            ctc_out, _, _ = _ctc_frames(model, batch, who=WHO, want_lse=False)
-            if ctc_out.shape[1] != -(-max(frames) // s):
-                raise ValueError(f"{WHO}: {ctc_out.shape[1]} encoder frames for windows of {max(frames)} feature frames at stride {s}")
+            ctc_out = encode_windows(model, feat, plan.start[a:b], plan.length[a:b], cmvn, s)
             out = ops.ctc_stitch(ctc_out, lo[a:b], hi[a:b], row[a:b], model.bos_index, rows=plan.rows, out=out)
     return out
+
+
+def encode_windows(model, feat, start, frames, cmvn, s):
+    """The CTC logits [len(start), max(frames) / s, V] of the windows feat[st : st + n] encoded as ONE batch, CMVN per window: what
+    `stitch_posteriors` runs per batch of windows and streaming.StreamingTranscriber per window as it completes (inside the caller's
+    no_grad).  start / frames: host lists, feature frames."""
+    from joeys2t_amd.alignment import _ctc_frames
+    from joeys2t_amd.batch import Batch
+    from joeys2t_amd.data_augmentation import finalize_features
+    dev = feat.device
+    chunk = torch.cat([feat[st:st + n] for st, n in zip(start, frames)])  # (overlapping windows: ragged, back to back)
+    off = torch.tensor(np.concatenate([[0], np.cumsum(frames)]), dtype=torch.int64, device=dev)
+    src, _ = finalize_features(chunk, off, frames, cmvn=cmvn, specaugment=None)
+    batch = Batch(src=src, src_length=torch.tensor(frames, dtype=torch.int64), src_prompt_mask=None, trg=None, trg_length=None,
+                  trg_prompt_mask=None, indices=torch.arange(len(start)), device=dev, pad_index=model.pad_index,
+                  eos_index=model.eos_index, is_train=False, task="S2T", n_gpu=1)
+    ctc_out, _, _ = _ctc_frames(model, batch, who=WHO, want_lse=False)
+    if ctc_out.shape[1] != -(-max(frames) // s):
+        raise ValueError(f"{WHO}: {ctc_out.shape[1]} encoder frames for windows of {max(frames)} feature frames at stride {s}")
+    return ctc_out
 
 
 def _threshold(silence_threshold) -> float:
@@ -161,23 +169,23 @@ def segment(blank_lp, argmax, *, blank: int, min_silence: Optional[int] = None, 
     return ops.PackedRows(seg_off[:n + 1].contiguous(), n, max(min(max_len, T), 1), T), seg_len[:n].contiguous()
 
 
-def _options(nbest_options, beam_size, n_best):
-    """(NBestOptions, return_parts, beam_size, n_best, the slots to search for) of the options transcribe_long hands on; every refusal
-    is a ValueError raised before the model is touched"""
+def _options(nbest_options, beam_size, n_best, who=WHO):
+    """(NBestOptions, return_parts, beam_size, n_best, the slots to search for) of the options transcribe_long - and, under its own
+    name `who`, streaming.CTCStreamDecoder - hands on; every refusal is a ValueError raised before the model is touched"""
     from joeys2t_amd import ctc_search
     o = dict(nbest_options)
     if "ctc_weight" in o:
-        raise ValueError(f"{WHO}: attention rescoring (ctc_weight) is not available over a recording: the decoder is not handed packed "
+        raise ValueError(f"{who}: attention rescoring (ctc_weight) is not available over a recording: the decoder is not handed packed "
                          "encoder rows (DESIGN 7), and a segment's frames come from several windows")
     return_parts, n_rescore = bool(o.pop("return_parts", False)), o.pop("n_rescore", None)
     known = dict(lm=None, lm_weight=0.0, length_bonus=0.0, lm_fusion="rescore", decision="map", mbr_scale=1.0, confidence=False,
                  confidence_scale=1.0, context=None, context_weight=0.0)
     if set(o) - set(known):
-        raise ValueError(f"{WHO}: unknown options {sorted(set(o) - set(known))}")
+        raise ValueError(f"{who}: unknown options {sorted(set(o) - set(known))}")
     o = {**known, **o}
-    opt = ctc_search.NBestOptions(WHO, o["lm"], o["lm_weight"], o["length_bonus"], o["lm_fusion"], o["decision"], o["mbr_scale"],
+    opt = ctc_search.NBestOptions(who, o["lm"], o["lm_weight"], o["length_bonus"], o["lm_fusion"], o["decision"], o["mbr_scale"],
                                   o["confidence"], o["confidence_scale"], o["context"], o["context_weight"])
-    return (opt, return_parts or opt.confidence, *ctc_search.nbest_slots(WHO, opt, beam_size, n_best, n_rescore))
+    return (opt, return_parts or opt.confidence, *ctc_search.nbest_slots(who, opt, beam_size, n_best, n_rescore))
 
 
 def decode_stream(model, stream, *, min_silence: Optional[int] = None, silence_threshold: float = 0.9, margin: int = 0,

@@ -1069,6 +1069,87 @@ def ctc_beam_search_ctx(logits3d, lse, cand_id, cand_lp, in_len, beam: int, n_be
     return ids, n, score, ctc, lms, ctx
 
 
+def ctc_stream_state(n_streams: int, beam: int, max_len: int, device) -> torch.Tensor:
+    """The state of n_streams fresh streams of js2t_ctc_stream_step: zero bytes, u8 [n_streams, stride].  state[b].zero_() resets
+    stream b.  beam and max_len belong to the state: every step over it takes the same two."""
+    total = lib().js2t_ctc_stream_state_bytes(int(n_streams), int(beam), int(max_len))
+    if total <= 0:
+        raise Js2tError(f"ctc_stream_state: {n_streams} streams, beam {beam}, max_len {max_len}: outside js2t_ctc_stream_step's limits")
+    return torch.zeros((int(n_streams), total // int(n_streams)), dtype=torch.uint8, device=device)
+
+
+_STREAM_FIELDS = (("fin_ids", torch.int64, "FNL"), ("fin_start", torch.int64, "F"), ("part_ids", torch.int64, "L"), ("part_start", torch.int64, ""),
+                  ("fin_len", torch.int32, "FN"), ("fin_score", torch.float32, "FN"), ("fin_ctc", torch.float32, "FN"),
+                  ("fin_lm", torch.float32, "FN"), ("fin_ctx", torch.int32, "FN"), ("fin_n", torch.int32, "F"), ("fin_why", torch.int32, "F"),
+                  ("consumed", torch.int32, ""), ("n_final", torch.int32, ""), ("part_len", torch.int32, ""), ("stable_len", torch.int32, ""))
+
+
+def ctc_stream_outputs(buf_or_device, n_streams: int, n_best: int, max_finals: int, max_len: int) -> dict:
+    """What js2t_ctc_stream_step writes, as views of ONE i64 buffer ("buf"), so that a single copy brings a call's whole result to the
+    host: the header's fin_* [B, max_finals, (n_best, (max_len))], consumed / n_final, part_* / stable_len.  buf_or_device: a device
+    to allocate the buffer on (zero-filled), or a buffer of this layout - the host copy of one - to take the views of."""
+    dims = {"F": int(max_finals), "N": int(n_best), "L": int(max_len)}
+    shapes = [(name, dt, (int(n_streams), *(dims[c] for c in spec))) for name, dt, spec in _STREAM_FIELDS]
+    words = [-(-math.prod(shape) * (8 if dt == torch.int64 else 4) // 8) for _, dt, shape in shapes]
+    buf = buf_or_device if isinstance(buf_or_device, torch.Tensor) else torch.zeros((sum(words),), dtype=torch.int64, device=buf_or_device)
+    if buf.dtype != torch.int64 or buf.shape != (sum(words),) or not buf.is_contiguous():
+        raise Js2tError(f"ctc_stream_outputs: a contiguous i64 [{sum(words)}] buffer expected")
+    out, at = {"buf": buf}, 0
+    for (name, dt, shape), w in zip(shapes, words):
+        out[name] = buf[at:at + w].view(dt)[:math.prod(shape)].view(shape)
+        at += w
+    return out
+
+
+def ctc_stream_step(state, rows, row_offsets, flush, *, beam: int, n_best: int, max_finals: int, max_len: int, blank: int, pad: int, lm=None,
+                    bos: int = 0, eos: int = 0, lm_weight: float = 0.0, length_bonus: float = 0.0, context=None, context_weight: float = 0.0,
+                    log_threshold: float = 0.0, min_silence: int = 0, out: dict = None) -> dict:
+    """One step of live CTC decoding over B = state.shape[0] streams (js2t_ctc_stream_step, which states the rule): state as
+    ctc_stream_state made it (updated in place); rows = (logits f32 [rows, V], lse f32 [rows], argmax i64 [rows], cand_id i64 /
+    cand_lp f32 [rows, n_cand]) - ctc_stitch's or row_lse's and ctc_beam_candidates' - the streams' new rows back to back;
+    row_offsets i32 [B + 1] and flush i32 [B] (or None) on the device.  lm / context and their weights: ctc_beam_search_ctx's;
+    log_threshold: the log of the blank's probability from which a frame is silent; min_silence 0: no endpoints.  Returns
+    ctc_stream_outputs' dict (out: one to write into - the same buffers every call, as a captured step needs).  No host read."""
+    who = "ctc_stream_step"
+    logits, lse, argmax, cand_id, cand_lp = rows
+    _dev(state, logits, lse, argmax, cand_id, cand_lp, row_offsets, flush)
+    if state.dim() != 2 or state.dtype != torch.uint8 or not state.is_contiguous():
+        raise Js2tError(f"{who}: the state ctc_stream_state made expected, got {state.dtype} {tuple(state.shape)}")
+    B = state.shape[0]
+    if B and state.numel() != lib().js2t_ctc_stream_state_bytes(B, int(beam), int(max_len)):
+        raise Js2tError(f"{who}: a state of {state.numel()} bytes is not that of {B} streams with beam {beam} and max_len {max_len}")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise Js2tError(f"{who}: contiguous f32 logits [rows, V] expected, got {logits.dtype} {tuple(logits.shape)}")
+    n_rows, V = logits.shape
+    if cand_id.dim() != 2 or cand_id.shape[0] != n_rows or cand_id.dtype != torch.int64 or not cand_id.is_contiguous() \
+            or cand_lp.shape != cand_id.shape or cand_lp.dtype != torch.float32 or not cand_lp.is_contiguous():
+        raise Js2tError(f"{who}: contiguous candidate tables i64 / f32 [{n_rows}, n_cand] expected, got "
+                        f"{cand_id.dtype} {tuple(cand_id.shape)} and {cand_lp.dtype} {tuple(cand_lp.shape)}")
+    if lse.shape != (n_rows,) or lse.dtype != torch.float32 or argmax.shape != (n_rows,) or argmax.dtype != torch.int64 \
+            or not lse.is_contiguous() or not argmax.is_contiguous():
+        raise Js2tError(f"{who}: contiguous lse f32 [{n_rows}] and argmax i64 [{n_rows}] expected")
+    if row_offsets.dtype != torch.int32 or row_offsets.shape != (B + 1,) or not row_offsets.is_contiguous():
+        raise Js2tError(f"{who}: row_offsets must be a contiguous int32 [{B + 1}] tensor, got {row_offsets.dtype} {tuple(row_offsets.shape)}")
+    if flush is not None and (flush.dtype != torch.int32 or flush.shape != (B,) or not flush.is_contiguous()):
+        raise Js2tError(f"{who}: flush must be a contiguous int32 [{B}] tensor, got {flush.dtype} {tuple(flush.shape)}")
+    dev = state.device
+    uni, table, capacity, max_probe, order_lm, _ = _lm_args(who, lm, lm_weight, dev, "state", V)
+    nodes, edges, ccap, cprobe, n_nodes, max_fail = _context_args(who, context, context_weight, dev, "state", V)
+    if int(n_best) < 1 or int(max_finals) < 1 or int(max_len) < 1:
+        raise Js2tError(f"{who}: n_best {n_best}, max_finals {max_finals} and max_len {max_len} must be at least 1")
+    o = out = ctc_stream_outputs(dev if out is None else out["buf"], B, n_best, max_finals, max_len)  # (a given buffer: its layout is checked)
+    _dev(o["buf"])
+    check(lib().js2t_ctc_stream_step(_p(logits), _p(lse), _p(argmax), _p(cand_id), _p(cand_lp), _p(row_offsets), _p(flush), _p(uni), _p(table),
+                                     capacity, max_probe, order_lm, _p(nodes), _p(edges), ccap, cprobe, n_nodes, max_fail, _p(state),
+                                     _p(o["fin_ids"]), _p(o["fin_len"]), _p(o["fin_score"]), _p(o["fin_ctc"]), _p(o["fin_lm"]), _p(o["fin_ctx"]),
+                                     _p(o["fin_start"]), _p(o["fin_n"]), _p(o["fin_why"]), _p(o["consumed"]), _p(o["n_final"]),
+                                     _p(o["part_ids"]), _p(o["part_len"]), _p(o["stable_len"]), _p(o["part_start"]), B, n_rows, V, int(beam),
+                                     cand_id.shape[1], int(n_best), int(max_finals), int(max_len), int(blank), int(pad), int(bos), int(eos),
+                                     float(lm_weight), float(context_weight), float(length_bonus), float(log_threshold), int(min_silence),
+                                     _stream()), "js2t_ctc_stream_step")
+    return out
+
+
 def context_rescore(ids, n, base_score, N: int, context, context_weight: float, Lp: int = None, out=None):
     """The contextual-biasing count of an n-best list (js2t_context_rescore): ids i64 [B, N, T] or [R, T], n i32 [B, N] or [R],
     base_score f32 [B, N] or [R] the last stage's score; context: a joeys2t_amd.biasing.ContextGraph on the tensors' device, or None
